@@ -3,7 +3,31 @@
 
   python bench.py [--gpus N --steps K --warmup W] [--tile 8192x8192]
                   [--kernel auto|stream|step2|vec4|scalar] [--spl S]
-                  [--numerics tolerance|bitwise]
+                  [--numerics tolerance|bitwise] [--dump-outputs DIR] [--full]
+
+A plain run does what `value` needs and no more: launch calibration, W warm-up
+steps, the settle steps, the K timed steps, the --dump-outputs files if asked
+for, and the result line (metric, value, unit, ms_per_step, the roofline
+fractions that follow from the timed launches, the launch plan).  Everything
+else described below -- every "aux" entry (the other collision, config 2, 4
+and 5, weak_slabs), the CPU baselines, roofline.device_copy and, at N > 1, the
+multi-rank self-check before the timed region -- is measured or checked only
+with --full (where --no-aux, --no-cpu-baseline, --no-strong and
+--no-d3q19 still drop single legs).
+
+--dump-outputs DIR: after the timed steps, what the timed engine holds after
+its last step is written as float32 .npy files: DIR/av_vels.npy (the K
+average velocities of the timed steps) and DIR/cells.npy (the lattice as
+[cell][9] populations; a lattice of more than DUMP_CELLS cells is reduced to a
+fixed, seeded sample of DUMP_CELLS cells in row-major order, 37.7 MB; at N > 1
+rank r writes its own block's share as DIR/cells_rank<r>.npy).  The start of
+the timed steps does not depend on the clock: after the settle steps (whose
+count follows the measured step time) the lattice is set back to equilibrium
+and the W warm-up steps run again, so the dumped state is always that of step
+W + K of the same problem and two builds can be compared value for value
+(to the last bit when both make the same launches: in tolerance mode a
+one-step remainder launch, W % S or K % S == 1, keeps the bitwise collision,
+so pin --spl for a bit-exact comparison).
 
 Numerics: `value` is measured with the collision
 --numerics names -- tolerance (default: LBM_FLAG_TOLERANCE, IEEE fp32 with one
@@ -527,7 +551,7 @@ def _check_cases(world: int):
 
 
 def multi_rank_check(rank: int, world: int, local_rank: int) -> dict:
-    """N > 1, untimed, before the timed region: the fused stream kernel over all
+    """N > 1 with --full, untimed, before the timed region: the fused stream kernel over all
     ranks (RCCL halos) against a single-domain run of the same library and mode
     on every rank's own GPU (each rank compares its own block bitwise; no
     gather).  Cases (_check_cases): a 2048^2 problem with random obstacles and a
@@ -722,10 +746,36 @@ def pick_spl(steps: int, requested: int, numerics: str = "bitwise", fused_remain
     return min(sorted(ms, reverse=True), key=est) if steps > 0 else max(ms)
 
 
+DUMP_CELLS = 1 << 20   # cells of a --dump-outputs lattice sample: x 9 fp32 = 37.7 MB of the 64 MB a dump may take
+DUMP_SEED = 20240607
+
+
+def dump_outputs(eng, out_dir: Path, steps: int, rank: int, world: int) -> np.ndarray:
+    """--dump-outputs: what a caller of the timed engine receives after its last
+    step, as float32 .npy files -- this rank's lattice block as [cell][9]
+    (cells.npy, cells_rank<r>.npy at N > 1; more than DUMP_CELLS / N cells: a
+    fixed, seeded sample of that many, in row-major order) and, from rank 0,
+    the av_vels of the timed steps.  Returns av_vels.  Every rank calls it
+    (the av_vels gather is collective at N > 1)."""
+    blocks, av = eng.store_local(n_av=steps)
+    flat = blocks[0].reshape(-1, native.Q) if len(blocks) == 1 else \
+        np.concatenate([b.reshape(-1, native.Q) for b in blocks])
+    keep = DUMP_CELLS // world
+    if flat.shape[0] > keep:
+        idx = np.random.default_rng(DUMP_SEED + rank).choice(flat.shape[0], size=keep, replace=False)
+        flat = flat[np.sort(idx)]
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / ("cells.npy" if world == 1 else f"cells_rank{rank}.npy"), np.ascontiguousarray(flat, np.float32))
+    if rank == 0:
+        np.save(out_dir / "av_vels.npy", np.asarray(av, np.float32))
+    return av
+
+
 def measure_weak(tnx: int, tny: int, R: int, C: int, args, kernel: int, kflags: int, rank: int, world: int,
-                 local_rank: int, dist_on: bool) -> dict:
+                 local_rank: int, dist_on: bool, dump_dir: str | None = None) -> dict:
     """K timed steps of the weak-scaling workload: R x C tiles of tnx x tny cells,
-    one per rank (R*C == world), after W warm-up and the settle steps."""
+    one per rank (R*C == world), after W warm-up and the settle steps.
+    dump_dir: write the timed engine's final state there (dump_outputs)."""
     import torch
     import torch.distributed as dist
     nx, ny = tnx * C, tny * R
@@ -761,6 +811,11 @@ def measure_weak(tnx: int, tny: int, R: int, C: int, args, kernel: int, kflags: 
         if nset > 0:
             eng.run_steps(nset)
             set_secs = eng.last_run_seconds()
+        # the settle count follows the clock, so start the timed steps from a
+        # state that does not: equilibrium again, then the W warm-up steps
+        eng.init_equilibrium()
+        if args.warmup > 0:
+            eng.run_steps(args.warmup, accelerate_first=True)
 
         def barrier():
             if dist_on:
@@ -778,7 +833,10 @@ def measure_weak(tnx: int, tny: int, R: int, C: int, args, kernel: int, kflags: 
             t = torch.tensor([elapsed, dev_secs], dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed, dev_secs = float(t[0]), float(t[1])
-        _, av = eng.store(cells=False, n_av=args.steps)
+        if dump_dir:
+            av = dump_outputs(eng, Path(dump_dir), args.steps, rank, world)
+        else:
+            _, av = eng.store(cells=False, n_av=args.steps)
         return {"nx": nx, "ny": ny, "elapsed": elapsed, "dev_secs": dev_secs, "finite": bool(np.all(np.isfinite(av))),
                 "kernel": eng.kernel_in_use(), "spl": eng.steps_per_launch(), "numerics": eng.numerics(),
                 "launches": eng.run_stats(), "calibration": cal,
@@ -898,6 +956,13 @@ def main() -> int:
                          "bit-identical to LastChance.cpp; the other mode is measured too (aux)")
     ap.add_argument("--no-calibrate", dest="calibrate", action="store_false",
                     help="pick S from the LAUNCH_MS fallback table instead of timing every S on this GPU first")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside `value`: the aux entries (other collision, configs 2, 4, "
+                         "5, weak_slabs), the CPU baselines, roofline.device_copy and the N > 1 self-check; off: only "
+                         "the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the timed engine's av_vels and lattice (a fixed, seeded sample "
+                         "when large) as float32 DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-aux", action="store_true")
     ap.add_argument("--no-d3q19", action="store_true")
@@ -933,7 +998,7 @@ def main() -> int:
     R, C = weak_grid(n, tnx, tny)
     mwd = main_watchdog(args.main_budget, rank, n)
     mrc = None
-    if dist_on:
+    if dist_on and args.full:
         try:
             mrc = multi_rank_check(rank, world, local_rank)
         except Exception as exc:  # recorded, never silently dropped
@@ -942,7 +1007,8 @@ def main() -> int:
         gate_multi_rank(mrc, rank, n, mwd)
     tol_main = args.numerics == "tolerance" and args.kernel in ("auto", "stream")
     kflags_main = kflags | (native.FLAG_TOLERANCE if tol_main else 0)
-    m = measure_weak(tnx, tny, R, C, args, kernel, kflags_main, rank, world, local_rank, dist_on)
+    m = measure_weak(tnx, tny, R, C, args, kernel, kflags_main, rank, world, local_rank, dist_on,
+                     dump_dir=args.dump_outputs)
     nx, ny, elapsed, dev_secs = m["nx"], m["ny"], m["elapsed"], m["dev_secs"]
     kernel_used, steps_per_launch = m["kernel"], m["spl"]
     if mwd is not None:
@@ -976,11 +1042,13 @@ def main() -> int:
     fracs = {"hbm": max(frac_pass, frac_counter or 0.0), "valu": frac_valu or 0.0}
     top = max(fracs, key=fracs.get)
     bound = top if fracs[top] >= BOUND_FRAC else "latency"
-    try:
-        copy = measure_copy_gbs(BYTES_PER_UPDATE // 2 * cells_per_gpu, local_rank)
-        copy["pass_vs_copy"] = round(achieved / copy["gbs"], 4)
-    except Exception as exc:  # context only: recorded, never fatal
-        copy = {"error": f"{type(exc).__name__}: {exc}"}
+    copy = None   # a run of its own: --full only
+    if args.full:
+        try:
+            copy = measure_copy_gbs(BYTES_PER_UPDATE // 2 * cells_per_gpu, local_rank)
+            copy["pass_vs_copy"] = round(achieved / copy["gbs"], 4)
+        except Exception as exc:  # context only: recorded, never fatal
+            copy = {"error": f"{type(exc).__name__}: {exc}"}
 
     out = {
         "metric": METRIC,
@@ -1017,7 +1085,7 @@ def main() -> int:
                      "effective_frac": round(effective / HBM_PEAK_GBS, 4),
                      # VALU instructions per launch and the pipe's busy fraction, same profile
                      "valu": prof.get("valu") or None, "profile": prof.get("profile"),
-                     # what a plain device copy of the same bytes reaches on this box, now
+                     # what a plain device copy of the same bytes reaches on this GPU, now (--full)
                      "device_copy": copy},
         "av_vels_finite": m["finite"],
         "numerics": m["numerics"],
@@ -1031,8 +1099,9 @@ def main() -> int:
         out["multi_rank_bitwise"] = bool(mrc.get("passed"))
         out["multi_rank_check"] = mrc
     aux = out.setdefault("aux", {})
-    watchdog = AuxWatchdog(args.aux_budget, out, rank)
-    if not args.no_aux and args.kernel in ("auto", "stream") and kernel_used == "stream":
+    watchdog = AuxWatchdog(args.aux_budget if args.full else 0, out, rank)
+    aux_on = args.full and not args.no_aux
+    if aux_on and args.kernel in ("auto", "stream") and kernel_used == "stream":
         # the same workload and step count with the other collision: bitwise
         # (LastChance.cpp arithmetic) when `value` is the tolerance mode, and
         # vice versa (LBM_FLAG_TOLERANCE, include/lbm_hip.h)
@@ -1052,7 +1121,7 @@ def main() -> int:
                               "tests/test_gpu_parity.py"})}
         except Exception as exc:
             aux[f"stream_{other}"] = {"error": str(exc)}
-    if n > 1 and not args.no_aux:
+    if n > 1 and aux_on:
         try:
             ms = measure_weak(tnx, tny, n, 1, args, kernel, kflags_main, rank, world, local_rank, dist_on)
             aux["weak_slabs"] = {"decomposition": f"{n}x1 (y slabs)", "global_grid": f"{ms['nx']}x{ms['ny']}",
@@ -1060,7 +1129,7 @@ def main() -> int:
                                  "ms_per_step": round(ms["elapsed"] / args.steps * 1e3, 5), "kernel": ms["kernel"]}
         except Exception as exc:
             aux["weak_slabs"] = {"error": str(exc)}
-    if not args.no_aux and not args.no_strong:
+    if aux_on and not args.no_strong:
         for key, slabs in (("config4_16384x16384", False), ("config4_slabs", True)):
             if slabs and n == 1:
                 continue
@@ -1069,7 +1138,7 @@ def main() -> int:
                                             flags=kflags_main & native.FLAG_TOLERANCE)
             except Exception as exc:
                 aux[key] = {"error": str(exc)}
-    if not args.no_aux and not args.no_d3q19:
+    if aux_on and not args.no_d3q19:
         try:
             aux["config5_d3q19"] = aux_d3q19(args.d3q19_n, D3Q19_STEPS, rank, world, local_rank, dist_on)
         except Exception as exc:
@@ -1080,7 +1149,7 @@ def main() -> int:
         except Exception as exc:
             aux["config5_d3q19_tolerance"] = {"error": str(exc)}
     if rank == 0 and n == 1:
-        if not args.no_aux:
+        if aux_on:
             try:
                 aux["config2_1024x1024"] = aux_1024(kernel, kflags, args.spl)
             except Exception as exc:
@@ -1089,7 +1158,7 @@ def main() -> int:
                 aux["config2_1024x1024_tolerance"] = aux_1024(kernel, kflags | native.FLAG_TOLERANCE, args.spl)
             except Exception as exc:
                 aux["config2_1024x1024_tolerance"] = {"error": str(exc)}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             for key, fn in (("cpu_baseline", cpu_baseline), ("cpu_config1_128x128", cpu_config1),
                             ("cpu_lastchance_1024x1024", cpu_lastchance_1024),
                             ("cpu_baseline_threads", cpu_baseline_threads)):

@@ -26,7 +26,8 @@ def run_bench(*args):
 
 
 def test_bench_json_contract():
-    d = run_bench("--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-aux")
+    # --full: roofline.device_copy is a run of its own, measured only there
+    d = run_bench("--full", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-aux")
     for k, t in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
                  ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str),
                  ("config", dict), ("roofline", dict)):
@@ -50,6 +51,40 @@ def test_bench_json_contract():
     assert d["av_vels_finite"] is True
     c = r["device_copy"]   # live context figure: a copy of the same bytes on this box
     assert 1000 < c["gbs"] < 8000 and c["pass_vs_copy"] == pytest.approx(r["achieved"] / c["gbs"], rel=1e-2)
+
+
+def test_bench_plain_run_and_dump(gpu_lib, tmp_path):
+    """A plain run (no --full) measures only `value`: no aux, no CPU baseline, no
+    device copy.  --dump-outputs writes the timed engine's state after its last
+    step, and that state is step W + K from equilibrium whatever the settle
+    count was: it equals an engine run here for exactly W + K steps, bit for
+    bit (seeded sample of DUMP_CELLS cells of the 2048 x 1024 lattice; --spl 4
+    with W and K multiples of 4, so both sides make the same launches -- in
+    tolerance mode a one-step remainder launch keeps the bitwise collision)."""
+    import numpy as np
+    sys.path.insert(0, str(ROOT))
+    import bench
+    W, K, S, nx, ny = 4, 12, 4, 2048, 1024
+    d = run_bench("--steps", str(K), "--warmup", str(W), "--tile", f"{nx}x{ny}", "--spl", str(S),
+                  "--dump-outputs", str(tmp_path / "o"))
+    assert "aux" not in d and "cpu_baseline" not in d and d["roofline"]["device_copy"] is None
+    assert d["steps"] == K and d["ms_per_step"] > 0 and d["av_vels_finite"] is True
+    assert d["value"] == pytest.approx(nx * ny / (d["ms_per_step"] * 1e-3) / 1e6, rel=2e-3)
+    assert sorted(f.name for f in (tmp_path / "o").iterdir()) == ["av_vels.npy", "cells.npy"]
+    cells, av = np.load(tmp_path / "o" / "cells.npy"), np.load(tmp_path / "o" / "av_vels.npy")
+    assert cells.dtype == np.float32 and cells.shape == (bench.DUMP_CELLS, 9) and cells.nbytes + av.nbytes <= 64e6
+    assert av.dtype == np.float32 and av.shape == (K,)
+    p = bench.lio.Params(nx, ny, K, 10, 0.1, 0.005, 1.85)
+    flags = gpu_lib.FLAG_TOLERANCE if d["numerics"] == "tolerance" else 0
+    with gpu_lib.Engine(p, bench.synthetic_obstacles(nx, ny), devices=[0], flags=flags, steps_per_launch=S) as e:
+        e.init_equilibrium()
+        e.run_steps(W, accelerate_first=True)
+        e.run_steps(K)
+        ref, ref_av = e.store(n_av=K)
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(nx * ny, size=bench.DUMP_CELLS, replace=False))
+    assert np.array_equal(cells, ref.reshape(-1, 9)[idx])
+    # av_vels: fp32 sums over 2 M cells whose order may differ with the launch geometry (smoke()'s bound)
+    np.testing.assert_allclose(av, ref_av, rtol=1e-5)
 
 
 @pytest.mark.parametrize("tolerance", [False, True])
