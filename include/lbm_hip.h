@@ -284,6 +284,29 @@ int lbm_load_cells_local(lbm_handle *h, const float *cells_aos_local);
 int lbm_store_local(lbm_handle *h, float *cells_aos_local, float *av_vels, int32_t n_av);
 int64_t lbm_local_cells(lbm_handle *h);
 
+/*
+ * Macroscopic fields of the current lattice, computed on the device: the
+ * u_x, u_y, |u| and pressure columns of final_state.dat without moving the
+ * nine populations to the host (lbm_store + writeResults move 36 B per cell
+ * and hold a second AoS lattice on the device; this moves 4 B per cell and
+ * requested field).
+ * Planar float[ny][nx] each, full domain; any pointer may be NULL (not
+ * computed).  RCCL: only this rank's rectangle is written.  Exactly the
+ * values lbmhost::writeResults derives from lbm_store's cells
+ * (LatticeBoltzmannUtils.hpp:221-281: sequential density sum, correctly
+ * rounded divide and sqrt; an obstacle cell gives 0, 0, 0, density * (1.f / 3.f)),
+ * bit for bit, whatever kernel or numerics mode advanced the lattice.
+ * LBM_E_STATE before lbm_load_cells / lbm_init_equilibrium.
+ */
+int lbm_store_fields(lbm_handle *h, float *ux, float *uy, float *speed, float *pressure);
+/* Local sub-domains only, each float[h][w], packed in lbm_local_rects order. */
+int lbm_store_fields_local(lbm_handle *h, float *ux, float *uy, float *speed, float *pressure);
+/* Sum over this handle's sub-domains of every cell's density (fp64
+ * accumulation of the fp32 per-cell sums) and the largest |u| of its fluid
+ * cells (0 when there are none).  Either pointer may be NULL.  Folded in a
+ * fixed order: two calls on the same lattice return identical bits. */
+int lbm_field_stats(lbm_handle *h, double *mass, float *max_speed);
+
 /* ≙ engine.readTensor("readTimer") (LbmRunner.cpp:133-144):
  * device-event seconds of the last lbm_run / lbm_run_steps. */
 int lbm_last_run_seconds(lbm_handle *h, double *seconds);
@@ -317,7 +340,8 @@ int lbm_placement_probe(lbm_handle *h, int32_t *kept, int32_t *tried, float *ms_
  * class -- e.g. "stream_steps2d S=10 tolerance", "... interior" / "...
  * boundary" on decomposed grids, "halo exchange WG (RCCL) + unpack",
  * "accelerate_row", "finalize_av", "resident_steps (all steps, one launch)",
- * the pipeline stages -- with its launch count and total / min / max ms
+ * the pipeline stages, "macroscopic_fields" (lbm_store_fields; lbm_field_stats:
+ * "macroscopic_fields stats") -- with its launch count and total / min / max ms
  * between the events around each launch.  *n_out = number of classes; at most
  * max_out entries are written.  LBM_E_STATE without the flag. */
 typedef struct lbm_kernel_time {

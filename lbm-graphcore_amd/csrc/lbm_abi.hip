@@ -167,6 +167,21 @@ int lbm_store_local(lbm_handle *h, float *cells_aos_local, float *av_vels, int32
     return guarded(h, [&] { h->store(cells_aos_local, av_vels, n_av, true); });
 }
 
+int lbm_store_fields(lbm_handle *h, float *ux, float *uy, float *speed, float *pressure) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->store_fields(ux, uy, speed, pressure); });
+}
+
+int lbm_store_fields_local(lbm_handle *h, float *ux, float *uy, float *speed, float *pressure) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->store_fields(ux, uy, speed, pressure, true); });
+}
+
+int lbm_field_stats(lbm_handle *h, double *mass, float *max_speed) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->field_stats(mass, max_speed); });
+}
+
 int64_t lbm_local_cells(lbm_handle *h) {
     if (!h) return -1;
     int64_t n = 0;

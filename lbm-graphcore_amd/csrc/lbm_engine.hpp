@@ -2,6 +2,8 @@
 // (include/lbm_hip.h), shared by its units:
 //   lbm_engine.hip        create, allocation, placement probe, the step loop,
 //                         load / store / destroy (the run path);
+//   lbm_fields.hip        macroscopic fields and lattice stats of the current
+//                         lattice (kernel; its host side is in lbm_engine.hip);
 //   lbm_exchange.hip      partition rule, torus neighbours, halo destinations,
 //                         the posted exchange (RCCL or device copies);
 //   lbm_split.hip         work decomposition: boundary / interior split,
@@ -70,6 +72,8 @@ hipError_t launch_aos_to_soa(const float *aos, float *f, long long P, int pitch,
 hipError_t launch_count_nonfinite(const float *f, long long P, int pitch, int w, int h, unsigned long long *out,
                                   hipStream_t s);
 hipError_t launch_soa_to_aos(const float *f, float *aos, long long P, int pitch, int w, int h, hipStream_t s);
+int fields_blocks(int w, int h);
+hipError_t launch_macroscopic_fields(const FieldsArgs &a, bool stats, hipStream_t s);
 hipError_t launch_halo_pack(const HaloArgs &a, hipStream_t s);
 hipError_t launch_halo_unpack(const HaloArgs &a, hipStream_t s);
 hipError_t resident_capacity(int variant, int device, bool tol, int &capacity);
@@ -396,5 +400,8 @@ struct lbm_handle {
     size_t aos_pitch(const Sub &s, bool local) const { return sizeof(float) * Q * (size_t)(local ? s.w : p.nx); }
     void load_cells(const float *aos, bool local = false);
     void store(float *aos, float *av, int n_av, bool local = false);
+    FieldsArgs fields_args(const Sub &s) const;
+    void store_fields(float *ux, float *uy, float *speed, float *pressure, bool local = false);
+    void field_stats(double *mass, float *max_speed);
     void destroy();
 };

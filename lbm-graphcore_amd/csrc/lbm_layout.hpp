@@ -243,6 +243,19 @@ struct HaloArgs {
     const float *recv[8];   // unpack: receive buffer per direction
 };
 
+// Macroscopic fields of the current lattice (lbm_fields.hip): planar staging
+// arrays float[h][sp], sp = roundup(w, 4); a null array is not computed.
+struct FieldsArgs {
+    const float *o;         // lattice origin
+    const uint8_t *obst;    // uint8[h][w]
+    long long plane;
+    int pitch, w, h, sp;
+    float obst_pressure;    // pressure reported for an obstacle cell: density * (1/3)
+    float *ux, *uy, *speed, *pressure;
+    double *mass_part;      // stats launch: per-block fp64 sums of the cells' densities
+    float *umax_part;       // stats launch: per-block max |u| over fluid cells
+};
+
 // message sizes (floats)
 inline int edge_len(int d, int w, int h) { return d < 4 ? ((d & 1) ? w : h) : 1; }
 inline long long msg_floats(int mode, int d, int w, int h, int g) {

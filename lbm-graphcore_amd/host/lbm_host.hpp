@@ -8,6 +8,7 @@
 //   reynoldsNumber          LatticeBoltzmannUtils.hpp:202-205
 //   writeAverageVelocities  LatticeBoltzmannUtils.hpp:208-219
 //   writeResults            LatticeBoltzmannUtils.hpp:221-281
+//   writeResultsFromFields  the same file from lbm_store_fields' planar arrays
 //   averageVelocity         LastChance.cpp:290-339 (used by compare_lbm)
 //   timedStep               main/include/GraphcoreUtils.hpp:130-138
 #pragma once
@@ -150,15 +151,34 @@ inline bool writeAverageVelocities(const std::string &filename, const std::vecto
     return true;
 }
 
+// one final_state.dat row: `ii jj u_x u_y |u| pressure obstacle`
+inline void writeResultsRow(std::ostream &file, size_t ii, size_t jj, const Macro &m, bool obstacle) {
+    file << ii << " " << jj << " " << std::setprecision(12) << std::scientific << m.ux << " " << m.uy << " " << m.u
+         << " " << m.pressure << " " << (int)obstacle << "\n";
+}
+
 inline bool writeResults(const std::string &filename, const Params &p, const Obstacles &o,
                          const std::vector<float> &cells) {
     std::ofstream file(filename);
     if (!file.is_open()) return false;
     for (size_t jj = 0; jj < p.ny; ++jj)
+        for (size_t ii = 0; ii < p.nx; ++ii) writeResultsRow(file, ii, jj, macroscopic(p, o, cells, ii, jj), o.at(ii, jj));
+    return true;
+}
+
+// final_state.dat from the planar float[ny][nx] fields of lbm_store_fields
+// (computed on the device: the values macroscopic() derives from the cells)
+inline bool writeResultsFromFields(const std::string &filename, const Params &p, const Obstacles &o,
+                                   const std::vector<float> &ux, const std::vector<float> &uy,
+                                   const std::vector<float> &u, const std::vector<float> &pressure) {
+    const size_t n = p.nx * p.ny;
+    if (ux.size() != n || uy.size() != n || u.size() != n || pressure.size() != n) return false;
+    std::ofstream file(filename);
+    if (!file.is_open()) return false;
+    for (size_t jj = 0; jj < p.ny; ++jj)
         for (size_t ii = 0; ii < p.nx; ++ii) {
-            const Macro m = macroscopic(p, o, cells, ii, jj);
-            file << ii << " " << jj << " " << std::setprecision(12) << std::scientific << m.ux << " " << m.uy << " "
-                 << m.u << " " << m.pressure << " " << (int)o.at(ii, jj) << "\n";
+            const size_t i = ii + jj * p.nx;
+            writeResultsRow(file, ii, jj, Macro{ux[i], uy[i], u[i], pressure[i]}, o.at(ii, jj));
         }
     return true;
 }

@@ -3,7 +3,7 @@
 //
 //   lbm_runner --params P --obstacles O [-n N] [--device gpu|loopback|cpu] [-d] [--exe ignored]
 //              [--runs 5] [--kernel auto|resident|stream|step2|vec4|scalar|pipeline] [--spl S] [--out-dir DIR]
-//              [--tolerance] [--json FILE]
+//              [--tolerance] [--device-fields] [--json FILE]
 //
 // Flow (same program numbering as the reference):
 //   load params/obstacles -> initialise cells on host -> create engine
@@ -12,14 +12,17 @@
 //   print ==done==, compute time, Reynolds number (av_vels[maxIters-1])
 //   then `runs` more lbm_run calls timed by device events (≙ readTimer),
 //   reported as MLUPS, GB/s and % of the HBM roofline (and, with --json, as
-//   one JSON record); -d creates the engine with LBM_FLAG_PROFILE and ends
+//   one JSON record); --device-fields makes run(2) lbm_store(av_vels only) +
+//   lbm_store_fields and writes final_state.dat from those planar fields (the
+//   same bytes); -d prints the lattice's total mass and peak |u| after the
+//   run (lbm_field_stats), creates the engine with LBM_FLAG_PROFILE and ends
 //   with a per-launch-class device-time summary (≙ engine.printProfileSummary,
 //   LbmRunner.cpp:115-122).
 // --device loopback places all N sub-domains on GPU 0 (the emulator analogue
 // of --device ipumodel: exercises the multi-GPU halo path on one device).
 // --device cpu runs the same fused step on the host's cores (lbm_cpu.hpp:
 // OpenMP rows, bitwise equal to the GPU engine's default numerics); the
-// GPU-only options (-n, --tolerance, --kernel, --spl, --graph-steps) do not
+// GPU-only options (-n, --tolerance, --kernel, --spl, --graph-steps, --device-fields) do not
 // apply there and are refused with a message.
 #include <cstdio>
 #include <cstdlib>
@@ -52,6 +55,8 @@ void usage(const char *exe) {
               << "                       library choice, 6; 10 with --tolerance)\n"
               << "      --tolerance      fp32 tolerance-mode collision (LBM_FLAG_TOLERANCE: one reciprocal of rho per\n"
               << "                       cell; not bit-identical to the reference, within the tolerance lbm_hip.h states)\n"
+              << "      --device-fields  final_state.dat from fields computed on the device (lbm_store_fields: u_x, u_y,\n"
+              << "                       |u|, pressure; 16 B per cell to the host instead of 36); same bytes in the file\n"
               << "      --out-dir arg    directory for av_vels.dat / final_state.dat (default: .)\n"
               << "      --graph-steps arg  replay the step loop as hipGraphs of 2*arg launches (0 = library default, <0 = off)\n"
               << "      --dump-partitioning arg  write the sub-domain decomposition as JSON\n"
@@ -119,7 +124,7 @@ int main(int argc, char *argv[]) {
     std::vector<std::string> gpuOnly;  // GPU-only options given on the command line
     int spl = 0;
     int numGpus = 1, runs = 5, graphSteps = 0;
-    bool debug = false, tolerance = false;
+    bool debug = false, tolerance = false, deviceFields = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         std::string val;
@@ -166,6 +171,9 @@ int main(int argc, char *argv[]) {
             gpuOnly.push_back(a);
         } else if (a == "--tolerance") {
             tolerance = true;
+            gpuOnly.push_back(a);
+        } else if (a == "--device-fields") {
+            deviceFields = true;
             gpuOnly.push_back(a);
         } else if (a == "--out-dir") {
             if (!next(outDir)) { usage(argv[0]); return EXIT_FAILURE; }
@@ -294,13 +302,35 @@ int main(int argc, char *argv[]) {
         lbmhost::check(lbm_load_cells(h, cells.data()), h, "lbm_load_cells");
     });
     total_compute_time += lbmhost::timedStep("Running LBM", [&]() { lbmhost::check(lbm_run(h), h, "lbm_run"); });
+    std::vector<float> f_ux, f_uy, f_u, f_pressure;  // --device-fields: final_state.dat's columns, planar
     lbmhost::timedStep("Running copy to host step", [&]() {
-        lbmhost::check(lbm_store(h, cells.data(), av_vels.data(), (int32_t)av_vels.size()), h, "lbm_store");
+        if (deviceFields) {
+            const size_t n = params->nx * params->ny;
+            for (auto *f : {&f_ux, &f_uy, &f_u, &f_pressure}) f->assign(n, 0.f);
+            lbmhost::check(lbm_store(h, nullptr, av_vels.data(), (int32_t)av_vels.size()), h, "lbm_store");
+            lbmhost::check(lbm_store_fields(h, f_ux.data(), f_uy.data(), f_u.data(), f_pressure.data()), h,
+                           "lbm_store_fields");
+        } else {
+            lbmhost::check(lbm_store(h, cells.data(), av_vels.data(), (int32_t)av_vels.size()), h, "lbm_store");
+        }
     });
     lbmhost::timedStep("Writing output files ", [&]() {
         lbmhost::writeAverageVelocities(outDir + "/av_vels.dat", av_vels);
-        lbmhost::writeResults(outDir + "/final_state.dat", *params, *obstacles, cells);
+        if (deviceFields)
+            lbmhost::writeResultsFromFields(outDir + "/final_state.dat", *params, *obstacles, f_ux, f_uy, f_u,
+                                            f_pressure);
+        else
+            lbmhost::writeResults(outDir + "/final_state.dat", *params, *obstacles, cells);
     });
+    if (debug) {
+        // the two numbers a run is watched by: total mass (conserved) and peak speed (Mach-number guard)
+        double mass = 0.0;
+        float maxSpeed = 0.f;
+        lbmhost::check(lbm_field_stats(h, &mass, &maxSpeed), h, "lbm_field_stats");
+        char line[96];
+        snprintf(line, sizeof(line), "mass: %.12e  max |u|: %.9e", mass, (double)maxSpeed);
+        std::cout << line << std::endl;
+    }
 
     std::cout << "==done==" << std::endl;
     std::cout << "Total compute time was \t" << std::right << std::setw(12) << std::setprecision(5)

@@ -5,6 +5,8 @@
 * init_cells            -- lbm::Cells::initialise    main/include/LatticeBoltzmannUtils.hpp:137-157
 * write_average_velocities -- writeAverageVelocities  LatticeBoltzmannUtils.hpp:208-219
 * write_results         -- writeResults              LatticeBoltzmannUtils.hpp:221-281
+* write_results_from_fields -- the same file from planar u_x, u_y, |u|, pressure
+                           arrays (Engine.fields(): lbm_store_fields)
 * reynolds_number       -- reynoldsNumber            LatticeBoltzmannUtils.hpp:202-205
 
 Error behaviour follows the reference: loaders return None (std::nullopt)
@@ -148,9 +150,15 @@ def write_average_velocities(filename: str, av_vels) -> bool:
 
 def write_results(filename: str, p: Params, obstacles: np.ndarray, cells: np.ndarray) -> bool:
     """final_state.dat: `ii jj u_x u_y |u| pressure obstacle`, jj outer, ii inner."""
-    ux, uy, u, pr = macroscopic(p, obstacles, cells)
+    return write_results_from_fields(filename, p, obstacles, *macroscopic(p, obstacles, cells))
+
+
+def write_results_from_fields(filename: str, p: Params, obstacles: np.ndarray, ux, uy, speed, pressure) -> bool:
+    """final_state.dat from the planar float32[ny][nx] fields (macroscopic(), or
+    Engine.fields() computed on the device): the bytes write_results writes."""
+    fields = [np.asarray(f, np.float32).reshape(p.ny, p.nx) for f in (ux, uy, speed, pressure)]
     jj, ii = np.meshgrid(np.arange(p.ny), np.arange(p.nx), indexing="ij")
-    cols = [ii.ravel(), jj.ravel(), ux.ravel(), uy.ravel(), u.ravel(), pr.ravel(), obstacles.ravel().astype(int)]
+    cols = [ii.ravel(), jj.ravel()] + [f.ravel() for f in fields] + [np.asarray(obstacles).ravel().astype(int)]
     try:
         with open(filename, "w") as f:
             f.writelines(f"{a} {b} {c:.12e} {d:.12e} {e:.12e} {g:.12e} {h}\n"

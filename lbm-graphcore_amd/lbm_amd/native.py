@@ -28,6 +28,7 @@ KERNEL_AUTO, KERNEL_SCALAR, KERNEL_VEC4, KERNEL_STEP2, KERNEL_STREAM, KERNEL_RES
 FLAG_FORCE_EXCHANGE, FLAG_ONE_STEP, FLAG_TOLERANCE, FLAG_PROFILE = 1, 2, 4, 8
 XFER_SEND, XFER_RECV, XFER_SELF = 0, 1, 2
 HALO_W1, HALO_WG = 1, 2
+FIELDS = ("ux", "uy", "speed", "pressure")   # argument order of lbm_store_fields
 
 # every symbol include/lbm_hip.h declares
 EXPORTED = [
@@ -35,6 +36,7 @@ EXPORTED = [
     "lbm_rccl_unique_id",
     "lbm_create", "lbm_create_ex", "lbm_load_cells", "lbm_init_equilibrium",
     "lbm_run", "lbm_run_steps", "lbm_store", "lbm_load_cells_local", "lbm_store_local", "lbm_local_cells",
+    "lbm_store_fields", "lbm_store_fields_local", "lbm_field_stats",
     "lbm_last_run_seconds",
     "lbm_total_free_cells", "lbm_local_rects", "lbm_kernel_in_use", "lbm_steps_per_launch",
     "lbm_run_stats", "lbm_profile_summary", "lbm_profile_reset", "lbm_placement_probe", "lbm_numerics", "lbm_nonfinite_count", "lbm_source_hash",
@@ -156,6 +158,9 @@ def load_library() -> ctypes.CDLL:
         "lbm_load_cells_local": ([H, f32p], ctypes.c_int),
         "lbm_store_local": ([H, f32p, f32p, i32], ctypes.c_int),
         "lbm_local_cells": ([H], i64),
+        "lbm_store_fields": ([H, f32p, f32p, f32p, f32p], ctypes.c_int),
+        "lbm_store_fields_local": ([H, f32p, f32p, f32p, f32p], ctypes.c_int),
+        "lbm_field_stats": ([H, ctypes.POINTER(ctypes.c_double), f32p], ctypes.c_int),
         "lbm_last_run_seconds": ([H, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
         "lbm_total_free_cells": ([H], i64),
         "lbm_local_rects": ([H, ctypes.POINTER(Rect), i32, i32p], ctypes.c_int),
@@ -345,6 +350,45 @@ class Engine:
             out.append(packed[off:off + w * h * Q].reshape(h, w, Q))
             off += w * h * Q
         return out, av[:n_av]
+
+    @staticmethod
+    def _which(which):
+        which = tuple(which)
+        bad = [n for n in which if n not in FIELDS]
+        if bad or len(set(which)) != len(which):
+            raise ValueError(f"fields are a subset of {FIELDS}, each at most once; got {which}")
+        return which
+
+    def fields(self, which=FIELDS):
+        """{name: float32[ny][nx]} of the requested macroscopic fields ("ux", "uy",
+        "speed", "pressure"), computed on the device from the current lattice
+        (lbm_store_fields): the values lio.macroscopic derives from store()'s
+        cells, bit for bit.  RCCL: only this rank's rectangle is written."""
+        which = self._which(which)
+        out = {n: np.zeros((self.params.ny, self.params.nx), np.float32) for n in which}
+        self._check(self._L.lbm_store_fields(self._h, *[_f32(out[n]) if n in out else None for n in FIELDS]))
+        return out
+
+    def fields_local(self, which=FIELDS):
+        """[{name: float32[h][w]}] per local rect (local_rects() order; lbm_store_fields_local)."""
+        which = self._which(which)
+        rects = self.local_rects()
+        n = int(self._L.lbm_local_cells(self._h))
+        packed = {f: np.zeros(n, np.float32) for f in which}
+        self._check(self._L.lbm_store_fields_local(self._h, *[_f32(packed[f]) if f in packed else None
+                                                              for f in FIELDS]))
+        out, off = [], 0
+        for (_, _, w, h) in rects:
+            out.append({f: packed[f][off:off + w * h].reshape(h, w) for f in which})
+            off += w * h
+        return out
+
+    def field_stats(self):
+        """(mass, max_speed) of this handle's sub-domains (lbm_field_stats): the fp64
+        sum of every cell's fp32 density and the largest |u| over fluid cells."""
+        mass, umax = ctypes.c_double(), ctypes.c_float()
+        self._check(self._L.lbm_field_stats(self._h, ctypes.byref(mass), ctypes.byref(umax)))
+        return mass.value, umax.value
 
     def last_run_seconds(self) -> float:
         s = ctypes.c_double()
