@@ -90,6 +90,11 @@ int lbm3d_run_steps(lbm3d_handle *h, int32_t steps);
  * av_vels[n_av] of the last run, combined over all ranks.  Either may be NULL. */
 int lbm3d_store(lbm3d_handle *h, float *cells_aos, float *av_vels, int32_t n_av);
 
+/* Velocity, |u| and pressure fields, plane / box extracts and mass / peak-speed
+ * statistics of the current lattice, computed on the device without moving
+ * the populations, are declared in lbm3d_fields_hip.h: lbm3d_store_fields,
+ * lbm3d_store_fields_box, lbm3d_field_stats. */
+
 /* Device-event seconds of the last lbm3d_run_steps. */
 int lbm3d_last_run_seconds(lbm3d_handle *h, double *seconds);
 

@@ -31,7 +31,8 @@
 #include <vector>
 #include <type_traits>
 
-#include "lbm3d_hip.h"
+#include "lbm3d_fields_hip.h"
+#include "lbm3d_fields.hpp"
 #include "lbm_packed.hpp"
 
 #ifndef LBM3D_XCD_REMAP
@@ -1917,6 +1918,115 @@ struct lbm3d_handle {
         }
     }
 
+    // ---- macroscopic fields / statistics of the current lattice (lbm3d_fields.hip) ----
+
+    // the cells [x0, x0+bx) x [y0, y0+by) x [z0, z0+bz) of slab s (z0 slab-local)
+    Fields3Args fields_args(const Slab &s, int x0, int y0, int z0, int bx, int by, int bz) const {
+        Fields3Args a{};
+        a.o = s.o[s.cur];
+        a.obst = s.obst;
+        a.PL = PL;
+        a.KS = KS;
+        a.px = px;
+        a.nx = p.nx;
+        a.ny = p.ny;
+        a.x0 = x0;
+        a.y0 = y0;
+        a.z0 = z0;
+        a.bx = bx;
+        a.by = by;
+        a.bz = bz;
+        a.quad = (x0 % 4 == 0 && bx >= 4) ? 1 : 0;  // every full-row box of a domain >= 4 cells wide
+        a.sp = a.quad ? (bx + 3) / 4 * 4 : bx;
+        a.obst_pressure = p.density * (1.f / 3.f);
+        return a;
+    }
+
+    // u_x, u_y, u_z, |u|, pressure of the box's cells into the packed planar
+    // host arrays float[b.nz][b.ny][b.nx] (host[i] NULL: field i is neither
+    // computed nor staged).  Slab by slab: the part of the box inside the slab
+    // is staged on its device (requested fields x cells; rows padded to 4
+    // floats on the 16-B path) and copied to its planes of the host arrays.
+    void store_fields_box(const lbm3d_box &b, float *const (&host)[5]) {
+        if (!loaded) throw fail3(LBM_E_STATE, "no lattice to derive fields from");
+        if (b.nx <= 0 || b.ny <= 0 || b.nz <= 0 || b.x0 < 0 || b.y0 < 0 || b.z0 < 0 ||
+            (long long)b.x0 + b.nx > p.nx || (long long)b.y0 + b.ny > p.ny || (long long)b.z0 + b.nz > p.nz)
+            throw fail3(LBM_E_INVALID, "box must be non-empty and inside the domain");
+        int want = 0;
+        for (float *f : host) want += f ? 1 : 0;
+        if (want == 0) return;
+        sync_all();
+        for (auto &s : slabs) {
+            const int zlo = std::max(b.z0, s.z0), zhi = std::min(b.z0 + b.nz, s.z0 + s.nzs);
+            if (zlo >= zhi) continue;
+            H3(hipSetDevice(s.dev));
+            Fields3Args a = fields_args(s, b.x0, b.y0, zlo - s.z0, b.nx, b.ny, zhi - zlo);
+            const size_t rows = (size_t)a.by * a.bz, field_floats = rows * a.sp;
+            float *stage = nullptr;
+            H3(hipMalloc(&stage, sizeof(float) * field_floats * want));
+            try {
+                float **dev[5] = {&a.ux, &a.uy, &a.uz, &a.speed, &a.pressure};
+                for (int i = 0, n = 0; i < 5; ++i)
+                    if (host[i]) *dev[i] = stage + field_floats * n++;
+                H3(launch_macroscopic_fields3d(a, false, s.s_comp));
+                H3(hipStreamSynchronize(s.s_comp));
+                const size_t off = (size_t)(zlo - b.z0) * b.ny * b.nx;
+                for (int i = 0; i < 5; ++i) {
+                    if (!host[i]) continue;
+                    if (a.sp == b.nx)  // no row padding: one contiguous copy
+                        H3(hipMemcpy(host[i] + off, *dev[i], sizeof(float) * field_floats, hipMemcpyDeviceToHost));
+                    else
+                        H3(hipMemcpy2D(host[i] + off, sizeof(float) * (size_t)b.nx, *dev[i], sizeof(float) * (size_t)a.sp,
+                                       sizeof(float) * (size_t)b.nx, rows, hipMemcpyDeviceToHost));
+                }
+            } catch (...) {
+                (void)hipFree(stage);
+                throw;
+            }
+            H3(hipFree(stage));
+        }
+    }
+
+    // Total mass (fp64 sum of every local cell's fp32 density) and the largest
+    // |u| over the local fluid cells.  The kernel leaves per-block partials;
+    // they are folded here in block order, slab after slab, so the same
+    // lattice always gives the same bits.
+    void field_stats(double *mass, float *max_speed) {
+        if (!loaded) throw fail3(LBM_E_STATE, "no lattice to take statistics of");
+        if (!mass && !max_speed) return;
+        sync_all();
+        double total = 0.0;
+        float umax = 0.f;
+        for (auto &s : slabs) {
+            H3(hipSetDevice(s.dev));
+            Fields3Args a = fields_args(s, 0, 0, 0, p.nx, p.ny, s.nzs);
+            const size_t nb = (size_t)fields3d_blocks(a);
+            // [nb doubles | nb floats]
+            void *part = nullptr;
+            H3(hipMalloc(&part, (sizeof(double) + sizeof(float)) * nb));
+            std::vector<double> hm(nb);
+            std::vector<float> hu(nb);
+            try {
+                a.mass_part = static_cast<double *>(part);
+                a.umax_part = reinterpret_cast<float *>(a.mass_part + nb);
+                H3(launch_macroscopic_fields3d(a, true, s.s_comp));
+                H3(hipStreamSynchronize(s.s_comp));
+                H3(hipMemcpy(hm.data(), a.mass_part, sizeof(double) * nb, hipMemcpyDeviceToHost));
+                H3(hipMemcpy(hu.data(), a.umax_part, sizeof(float) * nb, hipMemcpyDeviceToHost));
+            } catch (...) {
+                (void)hipFree(part);
+                throw;
+            }
+            H3(hipFree(part));
+            for (size_t i = 0; i < nb; ++i) {
+                total += hm[i];
+                umax = std::max(umax, hu[i]);
+            }
+        }
+        if (mass) *mass = total;
+        if (max_speed) *max_speed = umax;
+    }
+
     void destroy() {
         for (auto &s : slabs) {
             if (hipSetDevice(s.dev) != hipSuccess) continue;
@@ -2002,6 +2112,25 @@ int lbm3d_run_steps(lbm3d_handle *h, int32_t steps) {
 int lbm3d_store(lbm3d_handle *h, float *cells_aos, float *av_vels, int32_t n_av) {
     if (!h) return LBM_E_INVALID;
     return guard3(h, [&] { h->store(cells_aos, av_vels, n_av); });
+}
+
+int lbm3d_store_fields(lbm3d_handle *h, float *ux, float *uy, float *uz, float *speed, float *pressure) {
+    if (!h) return LBM_E_INVALID;
+    const lbm3d_box all{0, 0, 0, h->p.nx, h->p.ny, h->p.nz};
+    float *const host[5] = {ux, uy, uz, speed, pressure};
+    return guard3(h, [&] { h->store_fields_box(all, host); });
+}
+
+int lbm3d_store_fields_box(lbm3d_handle *h, const lbm3d_box *box, float *ux, float *uy, float *uz, float *speed,
+                           float *pressure) {
+    if (!h || !box) return LBM_E_INVALID;
+    float *const host[5] = {ux, uy, uz, speed, pressure};
+    return guard3(h, [&] { h->store_fields_box(*box, host); });
+}
+
+int lbm3d_field_stats(lbm3d_handle *h, double *mass, float *max_speed) {
+    if (!h) return LBM_E_INVALID;
+    return guard3(h, [&] { h->field_stats(mass, max_speed); });
 }
 
 int lbm3d_last_run_seconds(lbm3d_handle *h, double *seconds) {

@@ -8,6 +8,8 @@
 * write_results_from_fields -- the same file from planar u_x, u_y, |u|, pressure
                            arrays (Engine.fields(): lbm_store_fields)
 * reynolds_number       -- reynoldsNumber            LatticeBoltzmannUtils.hpp:202-205
+* macroscopic3d         -- the D3Q19 fields of include/lbm3d_fields_hip.h in fp32 numpy
+                           (Engine3D.fields(): lbm3d_store_fields)
 
 Error behaviour follows the reference: loaders return None (std::nullopt)
 and print the reference's message on stderr.  One deliberate strengthening:
@@ -136,6 +138,33 @@ def macroscopic(p: Params, obstacles: np.ndarray, cells: np.ndarray):
     u = np.where(ob, np.float32(0), u)
     pressure = np.where(ob, np.float32(p.density) * C_SQ, pressure).astype(np.float32)
     return ux, uy, u, pressure
+
+
+def macroscopic3d(p: Params3D, obstacles: np.ndarray, cells: np.ndarray):
+    """Per-cell (u_x, u_y, u_z, |u|, pressure), float32[nz][ny][nx] each, of the AoS D3Q19
+    cells float32[nz][ny][nx][19] in fp32 exactly as include/lbm3d_fields_hip.h defines
+    them (the expressions of oracle/lbm_oracle3d.c cell3d, sums sequential in the written
+    order); an obstacle cell gives +0, +0, +0, +0, density / 3."""
+    c = cells.astype(np.float32, copy=False)
+
+    def seq(*ks):
+        acc = c[..., ks[0]]
+        for k in ks[1:]:
+            acc = acc + c[..., k]
+        return acc
+
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rho = seq(*range(19))
+        ux = (seq(1, 5, 7, 10, 16) - seq(2, 6, 8, 11, 15)) / rho
+        uy = (seq(3, 5, 8, 12, 18) - seq(4, 6, 7, 13, 17)) / rho
+        uz = (seq(9, 10, 11, 12, 13) - seq(14, 15, 16, 17, 18)) / rho
+        u = np.sqrt(ux * ux + uy * uy + uz * uz, dtype=np.float32)
+    pressure = rho * C_SQ
+    ob = np.asarray(obstacles).reshape(rho.shape).astype(bool)
+    zero = np.float32(0)
+    ux, uy, uz, u = (np.where(ob, zero, f).astype(np.float32) for f in (ux, uy, uz, u))
+    pressure = np.where(ob, np.float32(p.density) * C_SQ, pressure).astype(np.float32)
+    return ux, uy, uz, u, pressure
 
 
 def write_average_velocities(filename: str, av_vels) -> bool:

@@ -48,6 +48,9 @@ EXPORTED3D = [
     "lbm3d_last_run_seconds", "lbm3d_total_free_cells", "lbm3d_local_slabs", "lbm3d_exchange_schedule",
     "lbm3d_last_error", "lbm3d_destroy",
 ]
+# every symbol include/lbm3d_fields_hip.h declares (D3Q19 fields, box extracts, stats)
+EXPORTED3D_FIELDS = ["lbm3d_store_fields", "lbm3d_store_fields_box", "lbm3d_field_stats"]
+FIELDS3D = ("ux", "uy", "uz", "speed", "pressure")   # argument order of lbm3d_store_fields
 Q3 = 19
 
 
@@ -92,6 +95,12 @@ class Params3D(ctypes.Structure):
     """lbm3d_params (include/lbm3d_hip.h)."""
     _fields_ = [("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("nz", ctypes.c_int32), ("max_iters", ctypes.c_int32),
                 ("density", ctypes.c_float), ("accel", ctypes.c_float), ("omega", ctypes.c_float)]
+
+
+class Box3D(ctypes.Structure):
+    """lbm3d_box (include/lbm3d_fields_hip.h): cells [x0, x0+nx) x [y0, y0+ny) x [z0, z0+nz)."""
+    _fields_ = [("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("z0", ctypes.c_int32),
+                ("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("nz", ctypes.c_int32)]
 
 
 class Rect(ctypes.Structure):
@@ -179,6 +188,9 @@ def load_library() -> ctypes.CDLL:
         "lbm3d_load_cells": ([H, f32p], ctypes.c_int),
         "lbm3d_run_steps": ([H, i32], ctypes.c_int),
         "lbm3d_store": ([H, f32p, f32p, i32], ctypes.c_int),
+        "lbm3d_store_fields": ([H, f32p, f32p, f32p, f32p, f32p], ctypes.c_int),
+        "lbm3d_store_fields_box": ([H, ctypes.POINTER(Box3D), f32p, f32p, f32p, f32p, f32p], ctypes.c_int),
+        "lbm3d_field_stats": ([H, ctypes.POINTER(ctypes.c_double), f32p], ctypes.c_int),
         "lbm3d_last_run_seconds": ([H, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
         "lbm3d_total_free_cells": ([H], i64),
         "lbm3d_local_slabs": ([H, i32p, i32p, i32, i32p], ctypes.c_int),
@@ -516,6 +528,42 @@ class Engine3D:
         av = np.zeros(max(int(n_av), 1), np.float32)
         self._check(self._L.lbm3d_store(self._h, _f32(out) if cells else None, _f32(av), int(n_av)))
         return out, av[:int(n_av)]
+
+    @staticmethod
+    def _which(which):
+        which = tuple(which)
+        bad = [n for n in which if n not in FIELDS3D]
+        if bad or len(set(which)) != len(which):
+            raise ValueError(f"fields are a subset of {FIELDS3D}, each at most once; got {which}")
+        return which
+
+    def fields(self, which=FIELDS3D):
+        """{name: float32[nz][ny][nx]} of the requested macroscopic fields ("ux", "uy",
+        "uz", "speed", "pressure"), computed on the device from the current lattice
+        (lbm3d_store_fields): the values lio.macroscopic3d derives from store()'s
+        cells, bit for bit.  RCCL: only this rank's planes are written."""
+        which = self._which(which)
+        out = {n: np.zeros((self.params.nz, self.params.ny, self.params.nx), np.float32) for n in which}
+        self._check(self._L.lbm3d_store_fields(self._h, *[_f32(out[n]) if n in out else None for n in FIELDS3D]))
+        return out
+
+    def fields_box(self, x0: int, y0: int, z0: int, nx: int, ny: int, nz: int, which=FIELDS3D):
+        """{name: float32[nz][ny][nx]} of the cells [x0, x0+nx) x [y0, y0+ny) x [z0, z0+nz)
+        (lbm3d_store_fields_box; a plane is a box of extent 1 along its normal).  No
+        periodic wrap: a box that is empty or leaves the domain raises LbmError."""
+        which = self._which(which)
+        box = Box3D(int(x0), int(y0), int(z0), int(nx), int(ny), int(nz))
+        out = {n: np.zeros((max(box.nz, 0), max(box.ny, 0), max(box.nx, 0)), np.float32) for n in which}
+        self._check(self._L.lbm3d_store_fields_box(self._h, ctypes.byref(box),
+                                                   *[_f32(out[n]) if n in out else None for n in FIELDS3D]))
+        return out
+
+    def field_stats(self):
+        """(mass, max_speed) of this handle's slabs (lbm3d_field_stats): the fp64 sum of
+        every cell's fp32 density and the largest |u| over fluid cells."""
+        mass, umax = ctypes.c_double(), ctypes.c_float()
+        self._check(self._L.lbm3d_field_stats(self._h, ctypes.byref(mass), ctypes.byref(umax)))
+        return mass.value, umax.value
 
     def last_run_seconds(self) -> float:
         s = ctypes.c_double()
