@@ -1,6 +1,8 @@
-// lbm_abi.hip -- the extern "C" functions of include/lbm_hip.h over the engine.
+// lbm_abi.hip -- the extern "C" functions of include/lbm_hip.h and the D2Q9
+// functions of include/lbm_forces_hip.h over the engine.
 
 #include "lbm_engine.hpp"
+#include "lbm_forces_hip.h"
 
 // --------------------------------------------------------------------------
 // C ABI
@@ -180,6 +182,26 @@ int lbm_store_fields_local(lbm_handle *h, float *ux, float *uy, float *speed, fl
 int lbm_field_stats(lbm_handle *h, double *mass, float *max_speed) {
     if (!h) return LBM_E_INVALID;
     return guarded(h, [&] { h->field_stats(mass, max_speed); });
+}
+
+int lbm_wall_force(lbm_handle *h, double *fx, double *fy, int64_t *links) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->wall_force(fx, fy, links); });
+}
+
+int lbm_store_wall_force(lbm_handle *h, float *fx, float *fy) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->store_wall_force(fx, fy); });
+}
+
+int lbm_set_bodies(lbm_handle *h, const int32_t *labels, int32_t nbodies) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->set_bodies(labels, nbodies); });
+}
+
+int lbm_body_forces(lbm_handle *h, double *fx, double *fy, int64_t *links, int32_t nbodies) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->body_forces(fx, fy, links, nbodies); });
 }
 
 int64_t lbm_local_cells(lbm_handle *h) {

@@ -1029,6 +1029,7 @@ void lbm_handle::field_stats(double *mass, float *max_speed) {
 void lbm_handle::destroy() {
     drop_graphs();
     prof_release();
+    forces_release();
     for (auto &s : subs) {
         if (hipSetDevice(s.dev) != hipSuccess) continue;
         (void)hipDeviceSynchronize();

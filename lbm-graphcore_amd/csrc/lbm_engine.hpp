@@ -4,6 +4,8 @@
 //                         load / store / destroy (the run path);
 //   lbm_fields.hip        macroscopic fields and lattice stats of the current
 //                         lattice (kernel; its host side is in lbm_engine.hip);
+//   lbm_forces.hip        momentum-exchange wall forces of the current lattice
+//                         (wall list, kernels and their host side);
 //   lbm_exchange.hip      partition rule, torus neighbours, halo destinations,
 //                         the posted exchange (RCCL or device copies);
 //   lbm_split.hip         work decomposition: boundary / interior split,
@@ -87,6 +89,9 @@ hipError_t launch_pipe_av(const float *partials, int n, float *av_local, int t, 
 hipError_t launch_resident(const ResidentArgs &a, int variant, bool tol, bool coop, hipStream_t s);
 hipError_t launch_resident_reduce(const float *partials, float *av_local, int steps, int ntiles, hipStream_t s);
 hipError_t launch_debug_spin(int microseconds, hipStream_t s);
+namespace forces {
+struct State;  // wall lists of a handle that asked for wall forces (lbm_forces.hip)
+}
 }  // namespace lbm
 
 namespace lbm {
@@ -403,5 +408,14 @@ struct lbm_handle {
     FieldsArgs fields_args(const Sub &s) const;
     void store_fields(float *ux, float *uy, float *speed, float *pressure, bool local = false);
     void field_stats(double *mass, float *max_speed);
+    // momentum-exchange wall forces (lbm_forces.hip; include/lbm_forces_hip.h)
+    lbm::forces::State *forces = nullptr;  // built at the first force call
+    void forces_build();
+    void forces_fill();
+    void forces_release();
+    void wall_force(double *fx, double *fy, int64_t *links);
+    void store_wall_force(float *fx, float *fy);
+    void set_bodies(const int32_t *labels, int32_t nbodies);
+    void body_forces(double *fx, double *fy, int64_t *links, int32_t nbodies);
     void destroy();
 };

@@ -10,6 +10,10 @@
 //   writeResults            LatticeBoltzmannUtils.hpp:221-281
 //   writeResultsFromFields  the same file from lbm_store_fields' planar arrays
 //   averageVelocity         LastChance.cpp:290-339 (used by compare_lbm)
+//   labelBodies, wallForces, writeForces
+//                           the momentum-exchange wall forces of
+//                           include/lbm_forces_hip.h on the host (lbm_runner
+//                           --forces; no reference counterpart)
 //   timedStep               main/include/GraphcoreUtils.hpp:130-138
 #pragma once
 
@@ -20,6 +24,7 @@
 #include <fstream>
 #include <iomanip>
 #include <iostream>
+#include <numeric>
 #include <optional>
 #include <string>
 #include <vector>
@@ -181,6 +186,95 @@ inline bool writeResultsFromFields(const std::string &filename, const Params &p,
             writeResultsRow(file, ii, jj, Macro{ux[i], uy[i], u[i], pressure[i]}, o.at(ii, jj));
         }
     return true;
+}
+
+// ---- momentum-exchange wall forces (include/lbm_forces_hip.h) ----
+
+// Connected components of the blocked cells: 8-connected, periodic, numbered
+// by each body's first cell in row-major order (lio.label_bodies' rule).
+// labels[ny][nx], -1 on fluid cells; returns the number of bodies.
+inline int32_t labelBodies(const Obstacles &o, std::vector<int32_t> &labels) {
+    const size_t n = o.nx * o.ny;
+    std::vector<size_t> parent(n);
+    std::iota(parent.begin(), parent.end(), (size_t)0);
+    auto find = [&](size_t i) {
+        while (parent[i] != i) i = parent[i] = parent[parent[i]];
+        return i;
+    };
+    for (size_t y = 0; y < o.ny; ++y)
+        for (size_t x = 0; x < o.nx; ++x) {
+            if (!o.at(x, y)) continue;
+            for (int dy = -1; dy <= 1; ++dy)
+                for (int dx = -1; dx <= 1; ++dx) {
+                    const size_t xx = (x + o.nx + dx) % o.nx, yy = (y + o.ny + dy) % o.ny;
+                    if (!o.at(xx, yy)) continue;
+                    const size_t a = find(y * o.nx + x), b = find(yy * o.nx + xx);
+                    if (a != b) parent[std::max(a, b)] = std::min(a, b);  // the root is the body's first cell
+                }
+        }
+    labels.assign(n, -1);
+    int32_t nbodies = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (!o.data[i]) continue;
+        const size_t r = find(i);
+        if (r == i) labels[i] = nbodies++;  // roots come first in row-major order
+        else labels[i] = labels[r];
+    }
+    return nbodies;
+}
+
+struct BodyForces {
+    std::vector<double> fx, fy;   // per body
+    std::vector<int64_t> links;
+    double total_fx = 0.0, total_fy = 0.0;
+    int64_t total_links = 0;
+};
+
+// Per-body and total wall forces of AoS cells: the per-cell fp32 expressions
+// of lbm_forces_hip.h, summed in fp64 in row-major order.
+inline BodyForces wallForces(const Params &p, const Obstacles &o, const std::vector<float> &cells,
+                             const std::vector<int32_t> &labels, int32_t nbodies) {
+    static const int ex[9] = {0, 1, 0, -1, 0, 1, -1, -1, 1};
+    static const int ey[9] = {0, 0, 1, 0, -1, 1, 1, -1, -1};
+    BodyForces r;
+    r.fx.assign(nbodies, 0.0);
+    r.fy.assign(nbodies, 0.0);
+    r.links.assign(nbodies, 0);
+    for (size_t y = 0; y < p.ny; ++y)
+        for (size_t x = 0; x < p.nx; ++x) {
+            if (!o.at(x, y)) continue;
+            const float *c = &cells[(x + y * p.nx) * NumSpeeds];
+            float t[9];
+            int nl = 0;
+            for (int j = 1; j < 9; ++j) {
+                const bool link = !o.at((x + p.nx + ex[j]) % p.nx, (y + p.ny + ey[j]) % p.ny);
+                t[j] = link ? c[j] : 0.f;
+                nl += link ? 1 : 0;
+            }
+            if (!nl) continue;
+            const float fx = ((t[3] + t[6] + t[7]) - (t[1] + t[5] + t[8])) * 2.f;
+            const float fy = ((t[4] + t[7] + t[8]) - (t[2] + t[5] + t[6])) * 2.f;
+            r.total_fx += (double)fx;
+            r.total_fy += (double)fy;
+            r.total_links += nl;
+            const int32_t b = labels[x + y * p.nx];
+            if (b >= 0 && b < nbodies) {
+                r.fx[b] += (double)fx;
+                r.fy[b] += (double)fy;
+                r.links[b] += nl;
+            }
+        }
+    return r;
+}
+
+// forces.dat: `body fx fy links` per body, then `total fx fy links`
+inline bool writeForces(const std::string &filename, const BodyForces &f) {
+    FILE *file = fopen(filename.c_str(), "w");
+    if (!file) return false;
+    for (size_t b = 0; b < f.fx.size(); ++b)
+        fprintf(file, "%zu %.12E %.12E %lld\n", b, f.fx[b], f.fy[b], (long long)f.links[b]);
+    fprintf(file, "total %.12E %.12E %lld\n", f.total_fx, f.total_fy, (long long)f.total_links);
+    return fclose(file) == 0;
 }
 
 template <class F>

@@ -3,7 +3,7 @@
 //
 //   lbm_runner --params P --obstacles O [-n N] [--device gpu|loopback|cpu] [-d] [--exe ignored]
 //              [--runs 5] [--kernel auto|resident|stream|step2|vec4|scalar|pipeline] [--spl S] [--out-dir DIR]
-//              [--tolerance] [--device-fields] [--json FILE]
+//              [--tolerance] [--device-fields] [--forces] [--json FILE]
 //
 // Flow (same program numbering as the reference):
 //   load params/obstacles -> initialise cells on host -> create engine
@@ -18,6 +18,11 @@
 //   run (lbm_field_stats), creates the engine with LBM_FLAG_PROFILE and ends
 //   with a per-launch-class device-time summary (≙ engine.printProfileSummary,
 //   LbmRunner.cpp:115-122).
+// --forces writes forces.dat after the run: the momentum-exchange force the
+// fluid put on each obstacle body in the last step (lbm_forces_hip.h; bodies
+// = 8-connected periodic components), one `body fx fy links` line per body and
+// a final `total` line -- through lbm_set_bodies / lbm_body_forces /
+// lbm_wall_force on the GPU, through lbmhost::wallForces with --device cpu.
 // --device loopback places all N sub-domains on GPU 0 (the emulator analogue
 // of --device ipumodel: exercises the multi-GPU halo path on one device).
 // --device cpu runs the same fused step on the host's cores (lbm_cpu.hpp:
@@ -35,6 +40,7 @@
 #include <vector>
 
 #include "lbm_cpu.hpp"
+#include "lbm_forces_hip.h"
 #include "lbm_host.hpp"
 
 namespace {
@@ -57,6 +63,8 @@ void usage(const char *exe) {
               << "                       cell; not bit-identical to the reference, within the tolerance lbm_hip.h states)\n"
               << "      --device-fields  final_state.dat from fields computed on the device (lbm_store_fields: u_x, u_y,\n"
               << "                       |u|, pressure; 16 B per cell to the host instead of 36); same bytes in the file\n"
+              << "      --forces         also write forces.dat: drag / lift per obstacle body (momentum exchange of the\n"
+              << "                       last step) and their total\n"
               << "      --out-dir arg    directory for av_vels.dat / final_state.dat (default: .)\n"
               << "      --graph-steps arg  replay the step loop as hipGraphs of 2*arg launches (0 = library default, <0 = off)\n"
               << "      --dump-partitioning arg  write the sub-domain decomposition as JSON\n"
@@ -77,7 +85,8 @@ std::string json_str(const std::string &v) {
 }
 
 // --device cpu: the reference's program sequence on the host backend
-int run_cpu(const lbmhost::Params &params, const lbmhost::Obstacles &obstacles, const std::string &outDir, int runs) {
+int run_cpu(const lbmhost::Params &params, const lbmhost::Obstacles &obstacles, const std::string &outDir, int runs,
+            bool forces) {
     std::cout << "Running on the host CPU (" << lbmcpu::Engine::threads()
               << " threads; bitwise numerics: the reference's LastChance.cpp arithmetic)" << std::endl;
     auto cells = lbmhost::initialiseCells(params);
@@ -94,6 +103,11 @@ int run_cpu(const lbmhost::Params &params, const lbmhost::Obstacles &obstacles, 
     lbmhost::timedStep("Writing output files ", [&]() {
         lbmhost::writeAverageVelocities(outDir + "/av_vels.dat", av_vels);
         lbmhost::writeResults(outDir + "/final_state.dat", params, obstacles, cells);
+        if (forces) {
+            std::vector<int32_t> labels;
+            const int32_t nbodies = lbmhost::labelBodies(obstacles, labels);
+            lbmhost::writeForces(outDir + "/forces.dat", lbmhost::wallForces(params, obstacles, cells, labels, nbodies));
+        }
     });
     std::cout << "==done==" << std::endl;
     std::cout << "Total compute time was \t" << std::right << std::setw(12) << std::setprecision(5)
@@ -124,7 +138,7 @@ int main(int argc, char *argv[]) {
     std::vector<std::string> gpuOnly;  // GPU-only options given on the command line
     int spl = 0;
     int numGpus = 1, runs = 5, graphSteps = 0;
-    bool debug = false, tolerance = false, deviceFields = false;
+    bool debug = false, tolerance = false, deviceFields = false, forces = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         std::string val;
@@ -175,6 +189,8 @@ int main(int argc, char *argv[]) {
         } else if (a == "--device-fields") {
             deviceFields = true;
             gpuOnly.push_back(a);
+        } else if (a == "--forces") {
+            forces = true;
         } else if (a == "--out-dir") {
             if (!next(outDir)) { usage(argv[0]); return EXIT_FAILURE; }
         } else if (a == "--graph-steps") {
@@ -246,7 +262,7 @@ int main(int argc, char *argv[]) {
             std::cerr << " (the host backend runs the reference arithmetic on one domain)" << std::endl;
             return EXIT_FAILURE;
         }
-        return run_cpu(*params, *obstacles, outDir, runs);
+        return run_cpu(*params, *obstacles, outDir, runs, forces);
     }
     const int ndev = lbm_device_count();
     if (ndev <= 0) {
@@ -303,6 +319,7 @@ int main(int argc, char *argv[]) {
     });
     total_compute_time += lbmhost::timedStep("Running LBM", [&]() { lbmhost::check(lbm_run(h), h, "lbm_run"); });
     std::vector<float> f_ux, f_uy, f_u, f_pressure;  // --device-fields: final_state.dat's columns, planar
+    lbmhost::BodyForces bodyForces;                   // --forces: forces.dat
     lbmhost::timedStep("Running copy to host step", [&]() {
         if (deviceFields) {
             const size_t n = params->nx * params->ny;
@@ -313,8 +330,23 @@ int main(int argc, char *argv[]) {
         } else {
             lbmhost::check(lbm_store(h, cells.data(), av_vels.data(), (int32_t)av_vels.size()), h, "lbm_store");
         }
+        if (forces) {
+            std::vector<int32_t> labels;
+            const int32_t nbodies = lbmhost::labelBodies(*obstacles, labels);
+            bodyForces.fx.assign(nbodies, 0.0);
+            bodyForces.fy.assign(nbodies, 0.0);
+            bodyForces.links.assign(nbodies, 0);
+            if (nbodies > 0) {
+                lbmhost::check(lbm_set_bodies(h, labels.data(), nbodies), h, "lbm_set_bodies");
+                lbmhost::check(lbm_body_forces(h, bodyForces.fx.data(), bodyForces.fy.data(), bodyForces.links.data(),
+                                               nbodies), h, "lbm_body_forces");
+            }
+            lbmhost::check(lbm_wall_force(h, &bodyForces.total_fx, &bodyForces.total_fy, &bodyForces.total_links), h,
+                           "lbm_wall_force");
+        }
     });
     lbmhost::timedStep("Writing output files ", [&]() {
+        if (forces) lbmhost::writeForces(outDir + "/forces.dat", bodyForces);
         lbmhost::writeAverageVelocities(outDir + "/av_vels.dat", av_vels);
         if (deviceFields)
             lbmhost::writeResultsFromFields(outDir + "/final_state.dat", *params, *obstacles, f_ux, f_uy, f_u,

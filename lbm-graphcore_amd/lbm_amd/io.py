@@ -10,6 +10,9 @@
 * reynolds_number       -- reynoldsNumber            LatticeBoltzmannUtils.hpp:202-205
 * macroscopic3d         -- the D3Q19 fields of include/lbm3d_fields_hip.h in fp32 numpy
                            (Engine3D.fields(): lbm3d_store_fields)
+* wall_links, wall_force_cells, wall_force (+ ...3d), label_bodies
+                        -- the momentum-exchange wall forces of include/lbm_forces_hip.h
+                           in fp32 numpy (Engine.wall_force(), .wall_force_field(), .body_forces())
 
 Error behaviour follows the reference: loaders return None (std::nullopt)
 and print the reference's message on stderr.  One deliberate strengthening:
@@ -165,6 +168,137 @@ def macroscopic3d(p: Params3D, obstacles: np.ndarray, cells: np.ndarray):
     ux, uy, uz, u = (np.where(ob, zero, f).astype(np.float32) for f in (ux, uy, uz, u))
     pressure = np.where(ob, np.float32(p.density) * C_SQ, pressure).astype(np.float32)
     return ux, uy, uz, u, pressure
+
+
+# ---- momentum-exchange wall forces (include/lbm_forces_hip.h) ----
+
+# speed vectors (x, y[, z]) in the speed order of lbm_hip.h / lbm3d_hip.h
+E2 = ((0, 0), (1, 0), (0, 1), (-1, 0), (0, -1), (1, 1), (-1, 1), (-1, -1), (1, -1))
+E3 = ((0, 0, 0), (1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (1, 1, 0), (-1, -1, 0), (1, -1, 0), (-1, 1, 0),
+      (0, 0, 1), (1, 0, 1), (-1, 0, 1), (0, 1, 1), (0, -1, 1),
+      (0, 0, -1), (-1, 0, -1), (1, 0, -1), (0, -1, -1), (0, 1, -1))
+
+
+def _links(obstacles, vectors):
+    ob = np.asarray(obstacles) != 0
+    axes = tuple(range(ob.ndim))
+    mask = np.zeros(ob.shape, np.uint32)
+    for j, e in enumerate(vectors[1:]):
+        # neighbour x + e_j, periodic: rolled[x] = ob[x + e]; array axes are (z,) y, x
+        nb = np.roll(ob, tuple(-c for c in reversed(e)), axes)
+        mask |= np.where(ob & ~nb, np.uint32(1 << j), np.uint32(0))
+    return mask
+
+
+def wall_links(obstacles) -> np.ndarray:
+    """uint32[ny][nx]: bit j-1 set iff the cell is blocked and its neighbour along e_j
+    (periodic) is not -- link j of include/lbm_forces_hip.h.  Non-zero = wall cell."""
+    return _links(np.asarray(obstacles).reshape(np.shape(obstacles)[-2:]), E2)
+
+
+def wall_links3d(obstacles) -> np.ndarray:
+    """uint32[nz][ny][nx] link masks of the D3Q19 lattice (bits 0..17)."""
+    return _links(obstacles, E3)
+
+
+def _gated(links, cells):
+    """t_j = link_j ? f_j : +0.f for every speed j (index 0 unused)."""
+    c = np.asarray(cells, np.float32)
+    zero = np.float32(0)
+    return [None] + [np.where((links >> np.uint32(j - 1)) & np.uint32(1), c[..., j], zero).astype(np.float32)
+                     for j in range(1, c.shape[-1])]
+
+
+def _seq(t, *ks):
+    acc = t[ks[0]]
+    for k in ks[1:]:
+        acc = acc + t[k]
+    return acc
+
+
+def wall_force_cells(obstacles, cells):
+    """Per-cell (fx, fy), float32[ny][nx] each: the momentum-exchange force on every wall
+    cell in fp32 exactly as include/lbm_forces_hip.h defines it, +0 elsewhere."""
+    links = wall_links(obstacles)
+    t = _gated(links, np.asarray(cells, np.float32).reshape(links.shape + (Q,)))
+    two = np.float32(2)
+    fx = (_seq(t, 3, 6, 7) - _seq(t, 1, 5, 8)) * two
+    fy = (_seq(t, 4, 7, 8) - _seq(t, 2, 5, 6)) * two
+    return fx.astype(np.float32), fy.astype(np.float32)
+
+
+def wall_force_cells3d(obstacles, cells):
+    """Per-cell (fx, fy, fz), float32[nz][ny][nx] each, of the D3Q19 lattice."""
+    links = wall_links3d(obstacles)
+    t = _gated(links, np.asarray(cells, np.float32).reshape(links.shape + (19,)))
+    two = np.float32(2)
+    fx = (_seq(t, 2, 6, 8, 11, 15) - _seq(t, 1, 5, 7, 10, 16)) * two
+    fy = (_seq(t, 4, 6, 7, 13, 17) - _seq(t, 3, 5, 8, 12, 18)) * two
+    fz = (_seq(t, 14, 15, 16, 17, 18) - _seq(t, 9, 10, 11, 12, 13)) * two
+    return fx.astype(np.float32), fy.astype(np.float32), fz.astype(np.float32)
+
+
+def _totals(links, comps, labels, nbodies):
+    nlinks = np.zeros(links.shape, np.int64)
+    for j in range(18):
+        nlinks += (links >> np.uint32(j)) & np.uint32(1)
+    total = tuple(float(np.sum(c, dtype=np.float64)) for c in comps) + (int(nlinks.sum()),)
+    if labels is None:
+        return total
+    lab = np.asarray(labels).reshape(links.shape)
+    if nbodies <= 0 or (lab[links != 0] >= nbodies).any():
+        raise ValueError("labels of wall cells must be < nbodies (negative: no body)")
+    sel = (links != 0) & (lab >= 0)
+    bodies = tuple(np.bincount(lab[sel], weights=c[sel].astype(np.float64), minlength=nbodies) for c in comps)
+    bodies += (np.bincount(lab[sel], weights=nlinks[sel], minlength=nbodies).astype(np.int64),)
+    return total, bodies
+
+
+def wall_force(obstacles, cells, labels=None, nbodies=0):
+    """(fx, fy, links): the fp64 sums of wall_force_cells over all wall cells and the
+    number of links.  With labels (int[ny][nx]; negative = no body) also the per-body
+    sums: ((fx, fy, links), (fx[nbodies], fy[nbodies], links[nbodies]))."""
+    return _totals(wall_links(obstacles), wall_force_cells(obstacles, cells), labels, nbodies)
+
+
+def wall_force3d(obstacles, cells, labels=None, nbodies=0):
+    """(fx, fy, fz, links) of the D3Q19 lattice; with labels also the per-body sums."""
+    return _totals(wall_links3d(obstacles), wall_force_cells3d(obstacles, cells), labels, nbodies)
+
+
+def label_bodies(obstacles):
+    """(labels int32, nbodies): the connected components of the blocked cells, periodic,
+    8-connected in 2-D and 26-connected in 3-D (cells that touch by a corner are one
+    body), numbered by each body's first cell in row-major order; fluid cells get -1."""
+    ob = np.asarray(obstacles) != 0
+    axes = tuple(range(ob.ndim))
+    n = int(ob.sum())
+    labels = np.full(ob.shape, -1, np.int32)
+    if n == 0:
+        return labels, 0
+    ids = np.full(ob.shape, -1, np.int64)
+    ids[ob] = np.arange(n)            # row-major rank among the blocked cells
+    shifts = [s for s in np.ndindex(*(3,) * ob.ndim) if any(c != 1 for c in s)]
+    pairs = []
+    for s in shifts:
+        nb = np.roll(ids, tuple(1 - c for c in s), axes)[ob]
+        pairs.append((np.nonzero(nb >= 0)[0], nb[nb >= 0]))
+    lab = np.arange(n)
+    while True:   # smallest rank of the neighbourhood, then pointer jumping, until nothing moves
+        new = lab.copy()
+        for me, other in pairs:
+            new[me] = np.minimum(new[me], lab[other])   # each cell once per direction
+        while True:
+            jump = new[new]
+            if np.array_equal(jump, new):
+                break
+            new = jump
+        if np.array_equal(new, lab):
+            break
+        lab = new
+    roots, inv = np.unique(lab, return_inverse=True)   # roots ascend: first cells in row-major order
+    labels[ob] = inv.astype(np.int32)
+    return labels, int(roots.size)
 
 
 def write_average_velocities(filename: str, av_vels) -> bool:

@@ -51,6 +51,11 @@ EXPORTED3D = [
 # every symbol include/lbm3d_fields_hip.h declares (D3Q19 fields, box extracts, stats)
 EXPORTED3D_FIELDS = ["lbm3d_store_fields", "lbm3d_store_fields_box", "lbm3d_field_stats"]
 FIELDS3D = ("ux", "uy", "uz", "speed", "pressure")   # argument order of lbm3d_store_fields
+# every symbol include/lbm_forces_hip.h declares (momentum-exchange wall forces, both engines)
+EXPORTED_FORCES = [
+    "lbm_wall_force", "lbm_store_wall_force", "lbm_set_bodies", "lbm_body_forces",
+    "lbm3d_wall_force", "lbm3d_store_wall_force", "lbm3d_set_bodies", "lbm3d_body_forces",
+]
 Q3 = 19
 
 
@@ -148,6 +153,7 @@ def load_library() -> ctypes.CDLL:
     f32p = ctypes.POINTER(ctypes.c_float)
     u8p = ctypes.POINTER(ctypes.c_uint8)
     i32p = ctypes.POINTER(ctypes.c_int32)
+    f64p, i64p = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
     sig = {
         "lbm_abi_version": ([], i32),
         "lbm_partition": ([i32, i32, i32, i32, i32, i32p, i32p, ctypes.POINTER(Rect)], ctypes.c_int),
@@ -191,6 +197,14 @@ def load_library() -> ctypes.CDLL:
         "lbm3d_store_fields": ([H, f32p, f32p, f32p, f32p, f32p], ctypes.c_int),
         "lbm3d_store_fields_box": ([H, ctypes.POINTER(Box3D), f32p, f32p, f32p, f32p, f32p], ctypes.c_int),
         "lbm3d_field_stats": ([H, ctypes.POINTER(ctypes.c_double), f32p], ctypes.c_int),
+        "lbm_wall_force": ([H, f64p, f64p, i64p], ctypes.c_int),
+        "lbm_store_wall_force": ([H, f32p, f32p], ctypes.c_int),
+        "lbm_set_bodies": ([H, i32p, i32], ctypes.c_int),
+        "lbm_body_forces": ([H, f64p, f64p, i64p, i32], ctypes.c_int),
+        "lbm3d_wall_force": ([H, f64p, f64p, f64p, i64p], ctypes.c_int),
+        "lbm3d_store_wall_force": ([H, f32p, f32p, f32p], ctypes.c_int),
+        "lbm3d_set_bodies": ([H, i32p, i32], ctypes.c_int),
+        "lbm3d_body_forces": ([H, f64p, f64p, f64p, i64p, i32], ctypes.c_int),
         "lbm3d_last_run_seconds": ([H, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
         "lbm3d_total_free_cells": ([H], i64),
         "lbm3d_local_slabs": ([H, i32p, i32p, i32, i32p], ctypes.c_int),
@@ -273,8 +287,87 @@ def rccl_unique_id() -> bytes:
     return bytes(buf)
 
 
-class Engine:
+class _WallForces:
+    """Engine / Engine3D methods over include/lbm_forces_hip.h; the class sets
+    _FORCE_PREFIX ("lbm_" / "lbm3d_") and _force_shape()."""
+
+    _nbodies = 0
+
+    def _force_fn(self, name):
+        return getattr(self._L, self._FORCE_PREFIX + name)
+
+    def wall_force(self):
+        """(fx, fy[, fz], links): the momentum-exchange force the fluid put on all wall
+        cells of this handle's sub-domains in the last step (fp64 sums of the fp32
+        per-cell values, folded in a fixed order) and the number of links."""
+        dims = len(self._force_shape())
+        f = [ctypes.c_double() for _ in range(dims)]
+        links = ctypes.c_int64()
+        self._check(self._force_fn("wall_force")(self._h, *[ctypes.byref(v) for v in f], ctypes.byref(links)))
+        return tuple(v.value for v in f) + (links.value,)
+
+    def wall_force_field(self):
+        """(fx, fy[, fz]): planar float32 maps of the per-cell force, +0 on every cell that
+        is no wall cell -- lio.wall_force_cells of store()'s cells, bit for bit.  RCCL:
+        only this rank's part is written."""
+        out = [np.zeros(self._force_shape(), np.float32) for _ in self._force_shape()]
+        self._check(self._force_fn("store_wall_force")(self._h, *[_f32(a) for a in out]))
+        return tuple(out)
+
+    def set_bodies(self, labels, nbodies: int) -> None:
+        """Assign blocked cells to bodies 0..nbodies-1 (labels: int32 map of the full
+        domain, e.g. lio.label_bodies; negative = no body).  set_bodies(None, 0) clears."""
+        if labels is None:
+            self._check(self._force_fn("set_bodies")(self._h, None, int(nbodies)))
+        else:
+            lab = np.ascontiguousarray(labels, dtype=np.int32)
+            if lab.size != int(np.prod(self._force_shape())):
+                raise ValueError("labels must cover the full domain")
+            self._check(self._force_fn("set_bodies")(self._h, lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                     int(nbodies)))
+        self._nbodies = int(nbodies) if labels is not None else 0
+
+    def body_forces(self):
+        """(fx[nbodies], fy[nbodies][, fz[nbodies]], links[nbodies]) of the bodies set last,
+        summed on the device."""
+        n = self._nbodies
+        dims = len(self._force_shape())
+        f = [np.zeros(max(n, 1), np.float64) for _ in range(dims)]
+        links = np.zeros(max(n, 1), np.int64)
+        self._check(self._force_fn("body_forces")(
+            self._h, *[a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) for a in f],
+            links.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n))
+        return tuple(a[:n] for a in f) + (links[:n],)
+
+
+class Engine(_WallForces):
     """One lbm_handle: the HIP counterpart of the reference's poplar::Engine."""
+
+    _FORCE_PREFIX = "lbm_"
+
+    def _force_shape(self):
+        return (self.params.ny, self.params.nx)
+
+    def force_history(self, steps: int, every: int, accelerate_first: bool = False):
+        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and sample
+        wall_force() after each chunk.  Returns (samples, av_vels): samples is a list of
+        (step, fx, fy, links) with step = steps done so far, av_vels the float32[steps]
+        concatenation of the chunks' average velocities.  accelerate_first applies to the
+        first chunk only.  In bitwise mode the lattice and av_vels equal those of one
+        run_steps(steps).  In tolerance mode a chunked run differs from an unchunked one
+        in the last bits: the steps of a chunk that do not fill a fused launch run as
+        remainder launches, and remainder launches are bitwise."""
+        steps, every = int(steps), int(every)
+        if steps < 0 or every < 1:
+            raise ValueError("steps >= 0 and every >= 1")
+        samples, av, done = [], [], 0
+        while done < steps:
+            n = min(every, steps - done)
+            self.run_steps(n, accelerate_first and done == 0)
+            av.append(self.store(cells=False, n_av=n)[1].copy())
+            done += n
+            samples.append((done,) + self.wall_force())
+        return samples, (np.concatenate(av) if av else np.zeros(0, np.float32))
 
     def __init__(self, params, obstacles: np.ndarray, num_gpus: int = 1, *, parts: int | None = None,
                  grid=(0, 0), transport: int = TRANSPORT_LOCAL, rank: int = 0, world: int = 1,
@@ -478,8 +571,13 @@ class Engine:
             pass
 
 
-class Engine3D:
+class Engine3D(_WallForces):
     """One lbm3d_handle: the D3Q19 extension engine (include/lbm3d_hip.h)."""
+
+    _FORCE_PREFIX = "lbm3d_"
+
+    def _force_shape(self):
+        return (self.params.nz, self.params.ny, self.params.nx)
 
     def __init__(self, params, obstacles: np.ndarray, *, parts: int = 1, transport: int = TRANSPORT_LOCAL,
                  rank: int = 0, world: int = 1, devices=None, unique_id: bytes | None = None, flags: int = 0):
