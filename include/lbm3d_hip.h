@@ -106,7 +106,7 @@ int lbm3d_local_slabs(lbm3d_handle *h, int32_t *z0, int32_t *nz, int32_t max_sla
 
 /*
  * The ordered ghost-exchange posts of z slab `rank` of `parts` (host-only;
- * the engine's RCCL exchanges iterate the same list, lbm3d.hip slab_posts):
+ * the engine's RCCL exchanges iterate the same list, lbm3d_abi.hip slab_posts):
  * send up (dir 0, +z), send down (dir 1), receive the below ghosts (dir 1),
  * receive the above ghosts (dir 0), periodic in z.  planes = 1: the five
  * speed planes leaving a face (one-step launches); 2 / 3: that many whole

@@ -1,0 +1,146 @@
+// lbm3d_abi.hip -- the extern "C" functions of include/lbm3d_hip.h,
+// include/lbm3d_fields_hip.h and the D3Q19 functions of
+// include/lbm_forces_hip.h over the engine (lbm3d_engine.hpp), and the
+// posting order of its RCCL ghost exchange.
+
+#include "lbm3d_engine.hpp"
+
+namespace lbm {
+std::array<lbm_xfer, 4> slab_posts(int rank, int world, long long floats) {
+    const int up = (rank + 1) % world, down = (rank + world - 1) % world;
+    return {lbm_xfer{LBM_XFER_SEND, 0, up, 0, floats}, lbm_xfer{LBM_XFER_SEND, 1, down, 0, floats},
+            lbm_xfer{LBM_XFER_RECV, 1, down, 0, floats}, lbm_xfer{LBM_XFER_RECV, 0, up, 0, floats}};
+}
+}  // namespace lbm
+
+using namespace lbm;
+
+namespace {
+thread_local std::string g_err3;
+}  // namespace
+
+extern "C" {
+
+int lbm3d_create(const lbm3d_params *params, const uint8_t *obstacles, const lbm_config *config, lbm3d_handle **out) {
+    if (!params || !out) return LBM_E_INVALID;
+    *out = nullptr;
+    auto *h = new (std::nothrow) lbm3d_handle();
+    if (!h) return LBM_E_NOMEM;
+    lbm_config dflt{};
+    dflt.parts = 1;
+    const int rc = guarded(h, [&] { h->create(params, obstacles, config ? *config : dflt); });
+    if (rc != LBM_OK) {
+        g_err3 = h->err;
+        h->destroy();
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return LBM_OK;
+}
+
+int lbm3d_init_equilibrium(lbm3d_handle *h) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->init_equilibrium(); });
+}
+
+int lbm3d_load_cells(lbm3d_handle *h, const float *cells_aos) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->load_cells(cells_aos); });
+}
+
+int lbm3d_run_steps(lbm3d_handle *h, int32_t steps) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->run_steps(steps); });
+}
+
+int lbm3d_store(lbm3d_handle *h, float *cells_aos, float *av_vels, int32_t n_av) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->store(cells_aos, av_vels, n_av); });
+}
+
+int lbm3d_store_fields(lbm3d_handle *h, float *ux, float *uy, float *uz, float *speed, float *pressure) {
+    if (!h) return LBM_E_INVALID;
+    const lbm3d_box all{0, 0, 0, h->p.nx, h->p.ny, h->p.nz};
+    return lbm3d_store_fields_box(h, &all, ux, uy, uz, speed, pressure);
+}
+
+int lbm3d_store_fields_box(lbm3d_handle *h, const lbm3d_box *box, float *ux, float *uy, float *uz, float *speed,
+                           float *pressure) {
+    if (!h || !box) return LBM_E_INVALID;
+    float *const host[5] = {ux, uy, uz, speed, pressure};
+    return guarded(h, [&] { h->store_fields_box(*box, host); });
+}
+
+int lbm3d_field_stats(lbm3d_handle *h, double *mass, float *max_speed) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->field_stats(mass, max_speed); });
+}
+
+int lbm3d_wall_force(lbm3d_handle *h, double *fx, double *fy, double *fz, int64_t *links) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->wall_force(fx, fy, fz, links); });
+}
+
+int lbm3d_store_wall_force(lbm3d_handle *h, float *fx, float *fy, float *fz) {
+    if (!h) return LBM_E_INVALID;
+    float *const host[3] = {fx, fy, fz};
+    return guarded(h, [&] { h->store_wall_force(host); });
+}
+
+int lbm3d_set_bodies(lbm3d_handle *h, const int32_t *labels, int32_t nbodies) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->set_bodies(labels, nbodies); });
+}
+
+int lbm3d_body_forces(lbm3d_handle *h, double *fx, double *fy, double *fz, int64_t *links, int32_t nbodies) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->body_forces(fx, fy, fz, links, nbodies); });
+}
+
+int lbm3d_last_run_seconds(lbm3d_handle *h, double *seconds) {
+    if (!h || !seconds) return LBM_E_INVALID;
+    *seconds = h->last_seconds;
+    return LBM_OK;
+}
+
+int64_t lbm3d_total_free_cells(lbm3d_handle *h) { return h ? h->free_cells : -1; }
+
+int lbm3d_local_slabs(lbm3d_handle *h, int32_t *z0, int32_t *nz, int32_t max_slabs, int32_t *n_out) {
+    if (!h) return LBM_E_INVALID;
+    const int n = (int)h->slabs.size();
+    if (n_out) *n_out = n;
+    for (int i = 0; i < n && i < max_slabs; ++i) {
+        if (z0) z0[i] = h->slabs[i].z0;
+        if (nz) nz[i] = h->slabs[i].nzs;
+    }
+    return LBM_OK;
+}
+
+int lbm3d_exchange_schedule(int32_t nx, int32_t ny, int32_t nz, int32_t parts, int32_t rank, int32_t planes,
+                            lbm_xfer *out, int32_t max_out, int32_t *n_out) {
+    if (!n_out || nx < 1 || ny < 1 || parts < 1 || parts > nz || rank < 0 || rank >= parts || planes < 1 ||
+        planes > 3)
+        return LBM_E_INVALID;
+    const long long KS = (long long)ny * ((nx + 15) / 16 * 16);  // the engine's speed stride (64-byte rows)
+    const auto v = slab_posts(rank, parts, planes == 1 ? 5 * KS : (long long)planes * Q3 * KS);
+    *n_out = (int32_t)v.size();
+    if (out) {
+        if (max_out < (int32_t)v.size()) return LBM_E_INVALID;
+        for (size_t i = 0; i < v.size(); ++i) out[i] = v[i];
+    }
+    return LBM_OK;
+}
+
+const char *lbm3d_last_error(lbm3d_handle *h) { return h ? h->err.c_str() : g_err3.c_str(); }
+
+void lbm3d_destroy(lbm3d_handle *h) {
+    if (!h) return;
+    try {
+        h->destroy();
+    } catch (...) {
+    }
+    delete h;
+}
+
+}  // extern "C"

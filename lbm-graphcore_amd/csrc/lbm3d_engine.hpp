@@ -1,0 +1,223 @@
+// lbm3d_engine.hpp -- declaration of the D3Q19 engine behind the C ABI
+// (include/lbm3d_hip.h), shared by its units:
+//   lbm3d.hip          the step kernels (one step per launch, two and three
+//                      steps per pass) and their launch_* wrappers;
+//   lbm3d_engine.hip   create, tuning knobs, allocation, placement probe, the
+//                      step loop, ghost exchange, load / store / destroy;
+//   lbm3d_fields.hip   macroscopic fields and lattice stats (kernel + host side);
+//   lbm3d_forces.hip   momentum-exchange wall forces (kernels + host side);
+//   lbm3d_abi.hip      the extern "C" functions and the RCCL posting order.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+
+#include <array>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "lbm3d_fields.hpp"
+#include "lbm3d_fields_hip.h"
+#include "lbm_common.hpp"
+#include "lbm_forces.hpp"
+#include "lbm_forces_hip.h"
+
+namespace lbm {
+
+constexpr int Q3 = 19;
+constexpr int GZ3 = 3;  // ghost planes each side of every slab lattice (and obst_g)
+
+struct Step3Args {
+    const float *fin;        // origin (plane z = 0) of the lattice read
+    float *fout;             // origin of the lattice written
+    const uint8_t *obst;     // [nzs][ny][nx]
+    long long PL, KS;        // plane stride, speed stride (floats)
+    int px, nx, ny;
+    int z0;                  // first plane of this launch
+    float omega, omo, w1, w2;
+    float *partials;         // this launch writes partials[block]
+};
+
+struct Two3Args {
+    const float *fin;   // origin of the lattice read (ghost planes -2, -1, nz, nz + 1 filled)
+    float *fout;
+    const uint8_t *obst;  // plane 0 of [nz + 6][ny][nx]: three planes of neighbour / periodic images each side
+    long long PL, KS;
+    int px, nx, ny, nz, seg;
+    int z0, zn;           // output planes [z0, zn) of this launch, in segments of seg planes
+    float omega, omo, w1, w2;
+    float k0, k1, k2;     // tolerance collision: omega / 3, omega / 18, omega / 36
+    float *partials;      // [2][nblocks]: |u| of step t+1, then t+2, at blk0 + this launch's block
+    int nblocks, blk0;
+};
+
+// Launchers of lbm3d.hip.  Each owns its grid; the *_blocks functions give the
+// blocks (= |u| partials) of the launch over the same arguments.  A launch
+// over no planes enqueues nothing and succeeds.
+// One step of `planes` planes from a.z0: step3d, or (pair) step3d_pair<zb, nt>.
+int step3d_blocks(int nx, int ny, int planes, bool pair, int zb);
+hipError_t launch_step3d(const Step3Args &a, int planes, bool pair, int zb, bool nt, hipStream_t s);
+// switch key of the instantiated step3d_two<TH, SKIP, PD> variants, -1 if none
+int two_variant(int th, bool skip, int pd);
+// n steps (n = 2, 3) of planes [a.z0, a.zn) in segments of a.seg planes:
+// step3d_two<12, false, variant> or (tol) its tolerance form; step3d_three<tol, skip>.
+int pass3d_blocks(int n, int nx, int ny, int planes, int seg);
+hipError_t launch_step3d_two(const Two3Args &a, int variant, bool tol, hipStream_t s);
+hipError_t launch_step3d_three(const Two3Args &a, bool tol, bool skip, hipStream_t s);
+hipError_t launch_reduce3d(const float *partials, int n, float *av_local, int t, hipStream_t s);
+hipError_t launch_init3d(float *base, long long planes, long long KS, long long PL, float c0, float c1, float c2,
+                         hipStream_t s);
+// AoS [nzs][ny][nx][19] staging <-> lattice interior, n cells
+hipError_t launch_aos_to_soa3d(const float *aos, float *f, long long PL, long long KS, int px, int nx, int ny,
+                               long long n, hipStream_t s);
+hipError_t launch_soa_to_aos3d(const float *f, float *aos, long long PL, long long KS, int px, int nx, int ny,
+                               long long n, hipStream_t s);
+hipError_t launch_debug_spin(int microseconds, hipStream_t s);  // lbm_kernels.hip
+
+// The ordered posts of one z slab's ghost exchange (RCCL pairs them by
+// order inside one ncclGroupStart/End): send up (dir 0, +z) to rank+1, send
+// down (dir 1, -z) to rank-1, receive the below ghosts (dir 1) from rank-1,
+// receive the above ghosts (dir 0) from rank+1 -- periodic in z.  `floats`
+// per message: 5 speed planes for a one-step launch, n whole planes (all 19
+// speeds) for an n-step pass.  post_exchange() posts exactly this list;
+// lbm3d_exchange_schedule exports it.  (lbm3d_abi.hip)
+std::array<lbm_xfer, 4> slab_posts(int rank, int world, long long floats);
+
+struct Slab {
+    int id = 0, dev = 0, z0 = 0, nzs = 0;
+    float *f[2] = {nullptr, nullptr};  // allocations (ghost plane below first)
+    bool f_joint = false;              // f[1] lies in f[0]'s allocation (LBM_LATTICE_PAD)
+    float *o[2] = {nullptr, nullptr};  // origins: plane z = 0
+    uint8_t *obst = nullptr;
+    uint8_t *obst_g = nullptr;   // [nzs + 6][ny][nx]: obst with three image planes each side (two/three-step kernels)
+    float *partials = nullptr;
+    int nblk_all = 0, nblk_bnd = 0, nblk_int = 0;
+    // n-step passes (n = 2, 3; index n - 2): |u| partials [n][nblk] and the blocks of one pass
+    float *pass_partials[2] = {nullptr, nullptr};
+    int pass_nblk[2] = {0, 0};
+    float *av_local = nullptr;
+    int av_cap = 0;
+    int cur = 0;
+    hipStream_t s_comp = nullptr, s_bnd = nullptr, s_comm = nullptr;
+    hipEvent_t ev_b = nullptr, ev_i = nullptr, ev_x = nullptr, ev_end = nullptr;
+};
+
+// one exchange's four message ends of a slab, as offsets (floats) from the
+// origin of the lattice exchanged, and the floats per message
+struct Ends3 {
+    long long up_src, down_src, ghost_lo, ghost_hi, floats;
+};
+
+}  // namespace lbm
+
+struct lbm3d_handle {
+    lbm3d_params p{};
+    int parts = 1, transport = LBM_TRANSPORT_LOCAL, rank = 0, world = 1;
+    int px = 0;
+    long long KS = 0, PL = 0;
+    bool pair = true;  // column-pair kernel (nx even; LBM3D_PAIR=0 forces the one-cell kernel)
+    // tuned at 512^3 (profiles/r01/d3q19/ab_zb_nt.log): 2 planes per block,
+    // non-temporal stores (the lattice written now is read a whole step later)
+    int zb = 2;        // LBM3D_ZB: planes per block of the pair kernel (1, 2, 4, 8)
+    bool nt = true;    // LBM3D_NT: non-temporal output stores
+    bool two = true;   // LBM3D_TWO: two steps per pass (step3d_two), single slab or z slabs
+    // LBM3D_THREE: three steps per pass (step3d_three), one slab or z slabs of
+    // >= 6 planes (needs two);
+    // default (-1): both modes since round 4 (with skip3) -- 512^3, skip3 on:
+    // tolerance 55.4-55.6 GLUPS, bitwise 51.2-51.3 vs 44.1-45.2 for two-step
+    // passes (profiles/r04/d3q19/ab_skip3.log); round 3, skip3 off, had kept
+    // bitwise on two-step passes (43.9-44.1 vs 44.6-45.0: the divisions made
+    // the third level's recompute VALU-bound)
+    int three = -1;
+    int seg3 = 64;     // LBM3D_SEG3: z planes per block of the three-step kernel
+    int seg = 64;      // LBM3D_SEG: z planes per block of the two-step kernel (32-128 equal within noise at 512^3)
+    int th = 12;       // LBM3D_TH: rows (waves) per block of the two-step kernel (12 only since round 3)
+    bool skip = false; // LBM3D_SKIP: waves skip the collisions of rows no later level reads (not faster)
+    // LBM3D_SKIP3: the same in the three-step pass -- there it pays (default on):
+    // the live rows per level (10, 8, 6 of 12) spread over the 4 SIMDs as
+    // 3 + 2 + 2 wave-collisions on the busiest SIMD instead of 3 + 3 + 3;
+    // 512^3 tolerance 55.4-55.6 vs 45.6-50.0 GLUPS, bitwise 51.2-51.3 vs 43.7-43.9
+    bool skip3 = true;
+    // LBM3D_PD: input planes in flight in the two-step kernel -- 0 (default): the
+    // next plane loaded once level 1 has consumed the current one (44.7 vs
+    // 38.6-42.5 GLUPS at 512^3 for 1, profiles/r03/d3q19/ab_pd.log); 1, 2
+    int pd = 0;
+    long long kspad = 0;  // LBM3D_KSPAD: floats appended to each speed plane (multiple of 64)
+    const char *lattice_pad = nullptr;  // LBM_LATTICE_PAD (debug knob)
+    bool poison = false;  // LBM_POISON=1: fresh allocations filled with NaN bytes
+    int probe_tries = 6;  // LBM3D_PLACEMENT_TRIES: lattice pairs the placement probe times (1 = off)
+    long long probe_min_cells = 1LL << 26;  // LBM3D_PROBE_MIN_CELLS: smallest single slab probed
+    bool probe_three = true;                 // LBM3D_PROBE_THREE=0: three-step engines skip the probe (A/B)
+    bool probe_log = false;  // LBM_PLACEMENT_LOG: print the probe's per-pair times
+    // ordering regression knobs (debug only, tests/test_gpu_ordering.py): slab
+    // LBM_DEBUG_DELAY_SUB's boundary and interior launches are each preceded
+    // by a stall of LBM_DEBUG_DELAY_US on their stream
+    int delay_sub = -1, delay_us = 0;
+    bool tolerance = false;  // LBM_FLAG_TOLERANCE: the two-step passes use cell3dt (not bitwise)
+    std::vector<lbm::Slab> slabs;
+    std::vector<int> all_z0, all_nz;
+    ncclComm_t comm = nullptr;
+    int64_t free_cells = 0;
+    bool loaded = false;
+    int last_steps = 0;
+    double last_seconds = 0.0;
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    std::string err;
+    // momentum-exchange wall forces (lbm_forces_hip.h): one wall list per slab, built at the first force call
+    std::vector<lbm::forces::WallList> walls;
+    bool walls_built = false;
+    int wall_bodies = 0;  // bodies set (0: none)
+
+    // several slabs, or RCCL transport (then even one rank sends its faces to
+    // itself through RCCL: the exchange path is testable on one GPU)
+    bool multi() const { return parts > 1 || transport == LBM_TRANSPORT_RCCL; }
+    float w1() const { return p.density * p.accel / 18.f; }
+    float w2() const { return p.density * p.accel / 36.f; }
+
+    // lbm3d_engine.hip
+    void read_tuning();
+    void create(const lbm3d_params *prm, const uint8_t *obstacles, const lbm_config &cfg);
+    void placement_probe();
+    void alloc(lbm::Slab &s, const uint8_t *obstacles);
+    void fill_fresh(void *ptr, size_t bytes, hipStream_t st) const;
+    int blocks_for(int planes) const { return lbm::step3d_blocks(p.nx, p.ny, planes, pair, zb); }
+    bool use_pass(int n) const;
+    bool use_two() const { return use_pass(2); }
+    bool use_three() const { return use_pass(3); }
+    std::vector<std::pair<int, int>> pass_ranges(int n, const lbm::Slab &s) const;
+    int pass_seg(int n) const { return n == 3 ? seg3 : seg; }
+    int pass_blocks(int n, int z0, int zn) const { return lbm::pass3d_blocks(n, p.nx, p.ny, zn - z0, pass_seg(n)); }
+    void launch_pass(int n, lbm::Slab &s, int z0, int zn, int blk0, hipStream_t st);
+    void reduce_pass(int n, lbm::Slab &s, int t, hipStream_t st);
+    void step_pass_multi(int n, int t);
+    void step_pass(int n, int t);
+    void ensure_av(int n);
+    lbm::Slab *local(int id);
+    lbm::Ends3 ends(const lbm::Slab &s, int n) const;
+    void post_exchange(int l, int n, bool use_comm);
+    void exchange(int l, bool use_comm);
+    void stall(const lbm::Slab &s, hipStream_t st);
+    void wait_x(lbm::Slab &s, hipStream_t st);
+    void launch(lbm::Slab &s, int zfirst, int planes, float *partials, hipStream_t st);
+    void step_once(int t);
+    void sync_all();
+    void refresh();
+    void run_steps(int steps);
+    void init_equilibrium();
+    void load_cells(const float *aos);
+    void store(float *aos, float *av, int n_av);
+    void destroy();
+    // lbm3d_fields.hip
+    lbm::Fields3Args fields_args(const lbm::Slab &s, int x0, int y0, int z0, int bx, int by, int bz) const;
+    void store_fields_box(const lbm3d_box &b, float *const (&host)[5]);
+    void field_stats(double *mass, float *max_speed);
+    // lbm3d_forces.hip
+    std::vector<uint8_t> obst_g_host(const lbm::Slab &s) const;
+    void walls_build();
+    void walls_release();
+    void wall_force(double *fx, double *fy, double *fz, int64_t *links);
+    void store_wall_force(float *const (&host)[3]);
+    void set_bodies(const int32_t *labels, int32_t nbodies);
+    void body_forces(double *fx, double *fy, double *fz, int64_t *links, int32_t nbodies);
+};

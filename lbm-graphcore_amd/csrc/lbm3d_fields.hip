@@ -2,7 +2,7 @@
 // engine on the device (include/lbm3d_fields_hip.h: lbm3d_store_fields,
 // lbm3d_store_fields_box, lbm3d_field_stats): u_x, u_y, u_z, |u| and pressure
 // of the current lattice, from each cell's 19 stored populations, without
-// moving them to the host.
+// moving them to the host.  The kernel, then the engine's host side.
 //
 // Memory-bound: 77 B read (19 populations + the obstacle byte) and at most
 // 20 B written per cell, no reuse, no LDS staging.  A box at least 4 cells
@@ -23,8 +23,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <vector>
 
-#include "lbm3d_fields.hpp"
+#include "lbm3d_engine.hpp"
 
 namespace lbm {
 
@@ -199,3 +200,85 @@ hipError_t launch_macroscopic_fields3d(const Fields3Args &a, bool stats, hipStre
 }
 
 }  // namespace lbm
+
+// ---- D3Q19 engine: host side ----
+
+using namespace lbm;
+
+// the cells [x0, x0+bx) x [y0, y0+by) x [z0, z0+bz) of slab s (z0 slab-local)
+Fields3Args lbm3d_handle::fields_args(const Slab &s, int x0, int y0, int z0, int bx, int by, int bz) const {
+    const int quad = (x0 % 4 == 0 && bx >= 4) ? 1 : 0;  // every full-row box of a domain >= 4 cells wide
+    // o, obst, strides, plane extents, box, quad, sp, obst_pressure; the output pointers stay null
+    return Fields3Args{s.o[s.cur], s.obst, PL, KS, px, p.nx, p.ny, x0, y0, z0, bx, by, bz,
+                       quad, quad ? (bx + 3) / 4 * 4 : bx, p.density * (1.f / 3.f)};
+}
+
+// u_x, u_y, u_z, |u|, pressure of the box's cells into the packed planar
+// host arrays float[b.nz][b.ny][b.nx] (host[i] NULL: field i is neither
+// computed nor staged).  Slab by slab: the part of the box inside the slab
+// is staged on its device (requested fields x cells; rows padded to 4
+// floats on the 16-B path) and copied to its planes of the host arrays.
+void lbm3d_handle::store_fields_box(const lbm3d_box &b, float *const (&host)[5]) {
+    if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to derive fields from");
+    if (b.nx <= 0 || b.ny <= 0 || b.nz <= 0 || b.x0 < 0 || b.y0 < 0 || b.z0 < 0 ||
+        (long long)b.x0 + b.nx > p.nx || (long long)b.y0 + b.ny > p.ny || (long long)b.z0 + b.nz > p.nz)
+        throw lbm_failure(LBM_E_INVALID, "box must be non-empty and inside the domain");
+    int want = 0;
+    for (float *f : host) want += f ? 1 : 0;
+    if (want == 0) return;
+    sync_all();
+    for (auto &s : slabs) {
+        const int zlo = std::max(b.z0, s.z0), zhi = std::min(b.z0 + b.nz, s.z0 + s.nzs);
+        if (zlo >= zhi) continue;
+        HIP_CHECK(hipSetDevice(s.dev));
+        Fields3Args a = fields_args(s, b.x0, b.y0, zlo - s.z0, b.nx, b.ny, zhi - zlo);
+        const size_t rows = (size_t)a.by * a.bz, field_floats = rows * a.sp;
+        const DeviceStage stage(sizeof(float) * field_floats * want);
+        float **dev[5] = {&a.ux, &a.uy, &a.uz, &a.speed, &a.pressure};
+        for (int i = 0, n = 0; i < 5; ++i)
+            if (host[i]) *dev[i] = stage.as<float>() + field_floats * n++;
+        HIP_CHECK(launch_macroscopic_fields3d(a, false, s.s_comp));
+        HIP_CHECK(hipStreamSynchronize(s.s_comp));
+        const size_t off = (size_t)(zlo - b.z0) * b.ny * b.nx;
+        for (int i = 0; i < 5; ++i) {
+            if (!host[i]) continue;
+            if (a.sp == b.nx)  // no row padding: one contiguous copy
+                HIP_CHECK(hipMemcpy(host[i] + off, *dev[i], sizeof(float) * field_floats, hipMemcpyDeviceToHost));
+            else
+                HIP_CHECK(hipMemcpy2D(host[i] + off, sizeof(float) * (size_t)b.nx, *dev[i], sizeof(float) * (size_t)a.sp,
+                                      sizeof(float) * (size_t)b.nx, rows, hipMemcpyDeviceToHost));
+        }
+    }
+}
+
+// Total mass (fp64 sum of every local cell's fp32 density) and the largest
+// |u| over the local fluid cells.  The kernel leaves per-block partials;
+// they are folded here in block order, slab after slab, so the same
+// lattice always gives the same bits.
+void lbm3d_handle::field_stats(double *mass, float *max_speed) {
+    if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to take statistics of");
+    if (!mass && !max_speed) return;
+    sync_all();
+    double total = 0.0;
+    float umax = 0.f;
+    for (auto &s : slabs) {
+        HIP_CHECK(hipSetDevice(s.dev));
+        Fields3Args a = fields_args(s, 0, 0, 0, p.nx, p.ny, s.nzs);
+        const size_t nb = (size_t)fields3d_blocks(a);
+        const DeviceStage part((sizeof(double) + sizeof(float)) * nb);  // [nb doubles | nb floats]
+        std::vector<double> hm(nb);
+        std::vector<float> hu(nb);
+        a.mass_part = part.as<double>();
+        a.umax_part = reinterpret_cast<float *>(a.mass_part + nb);
+        HIP_CHECK(launch_macroscopic_fields3d(a, true, s.s_comp));
+        HIP_CHECK(hipStreamSynchronize(s.s_comp));
+        HIP_CHECK(hipMemcpy(hm.data(), a.mass_part, sizeof(double) * nb, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(hu.data(), a.umax_part, sizeof(float) * nb, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < nb; ++i) {
+            total += hm[i];
+            umax = std::max(umax, hu[i]);
+        }
+    }
+    if (mass) *mass = total;
+    if (max_speed) *max_speed = umax;
+}

@@ -1,5 +1,5 @@
 // lbm3d_fields.hpp -- argument block and launcher of the D3Q19 macroscopic
-// fields kernel (lbm3d_fields.hip), shared with the engine (lbm3d.hip).
+// fields kernel (lbm3d_fields.hip), part of the engine's declaration (lbm3d_engine.hpp).
 #pragma once
 
 #include <hip/hip_runtime.h>

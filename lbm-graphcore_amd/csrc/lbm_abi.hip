@@ -9,26 +9,6 @@
 // --------------------------------------------------------------------------
 namespace {
 thread_local std::string g_create_error;
-
-template <class F>
-int guarded(lbm_handle *h, F &&f) {
-    try {
-        f();
-        return LBM_OK;
-    } catch (const lbm_failure &e) {
-        if (h) h->err = e.what();
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        if (h) h->err = "host allocation failed";
-        return LBM_E_NOMEM;
-    } catch (const std::exception &e) {
-        if (h) h->err = e.what();
-        return LBM_E_INTERNAL;
-    } catch (...) {
-        if (h) h->err = "unknown failure";
-        return LBM_E_INTERNAL;
-    }
-}
 }  // namespace
 
 extern "C" {

@@ -862,15 +862,13 @@ void lbm_handle::load_cells(const float *aos, bool local) {
     for (size_t k = 0; k < subs.size(); ++k) {
         Sub &s = subs[k];
         set_device(s);
-        float *stage = nullptr;
         const size_t row_bytes = sizeof(float) * Q * (size_t)s.w;
-        HIP_CHECK(hipMalloc(&stage, row_bytes * (size_t)s.h));
-        HIP_CHECK(hipMemcpy2D(stage, row_bytes, aos_of(aos, k, local), aos_pitch(s, local), row_bytes, (size_t)s.h,
+        const DeviceStage stage(row_bytes * (size_t)s.h);
+        HIP_CHECK(hipMemcpy2D(stage.get(), row_bytes, aos_of(aos, k, local), aos_pitch(s, local), row_bytes, (size_t)s.h,
                               hipMemcpyHostToDevice));
         s.cur = 0;
-        HIP_CHECK(launch_aos_to_soa(stage, s.o[0], s.plane, s.pitch, s.w, s.h, s.s_comp));
+        HIP_CHECK(launch_aos_to_soa(stage.as<float>(), s.o[0], s.plane, s.pitch, s.w, s.h, s.s_comp));
         HIP_CHECK(hipStreamSynchronize(s.s_comp));
-        HIP_CHECK(hipFree(stage));
     }
     refresh_halos();
     sync_all();
@@ -885,14 +883,12 @@ void lbm_handle::store(float *aos, float *av, int n_av, bool local) {
         for (size_t k = 0; k < subs.size(); ++k) {
             Sub &s = subs[k];
             set_device(s);
-            float *stage = nullptr;
             const size_t row_bytes = sizeof(float) * Q * (size_t)s.w;
-            HIP_CHECK(hipMalloc(&stage, row_bytes * (size_t)s.h));
-            HIP_CHECK(launch_soa_to_aos(s.o[s.cur], stage, s.plane, s.pitch, s.w, s.h, s.s_comp));
+            const DeviceStage stage(row_bytes * (size_t)s.h);
+            HIP_CHECK(launch_soa_to_aos(s.o[s.cur], stage.as<float>(), s.plane, s.pitch, s.w, s.h, s.s_comp));
             HIP_CHECK(hipStreamSynchronize(s.s_comp));
-            HIP_CHECK(hipMemcpy2D(const_cast<float *>(aos_of(aos, k, local)), aos_pitch(s, local), stage, row_bytes,
+            HIP_CHECK(hipMemcpy2D(const_cast<float *>(aos_of(aos, k, local)), aos_pitch(s, local), stage.get(), row_bytes,
                                   row_bytes, (size_t)s.h, hipMemcpyDeviceToHost));
-            HIP_CHECK(hipFree(stage));
         }
     }
     if (av && n_av > 0) {
@@ -902,12 +898,10 @@ void lbm_handle::store(float *aos, float *av, int n_av, bool local) {
             if (transport == LBM_TRANSPORT_RCCL) {
                 Sub &s = subs[0];
                 set_device(s);
-                float *gath = nullptr;
-                HIP_CHECK(hipMalloc(&gath, sizeof(float) * (size_t)n * world));
-                NCCL_CHECK(ncclAllGather(s.av_local, gath, (size_t)n, ncclFloat, comm, s.s_comm));
+                const DeviceStage gath(sizeof(float) * (size_t)n * world);
+                NCCL_CHECK(ncclAllGather(s.av_local, gath.get(), (size_t)n, ncclFloat, comm, s.s_comm));
                 HIP_CHECK(hipStreamSynchronize(s.s_comm));
-                HIP_CHECK(hipMemcpy(per.data(), gath, sizeof(float) * (size_t)n * world, hipMemcpyDeviceToHost));
-                HIP_CHECK(hipFree(gath));
+                HIP_CHECK(hipMemcpy(per.data(), gath.get(), sizeof(float) * (size_t)n * world, hipMemcpyDeviceToHost));
             } else {
                 for (auto &s : subs) {
                     set_device(s);
@@ -927,103 +921,6 @@ void lbm_handle::store(float *aos, float *av, int n_av, bool local) {
             av[t] = tot / fc;
         }
     }
-}
-
-FieldsArgs lbm_handle::fields_args(const Sub &s) const {
-    FieldsArgs a{};
-    a.o = s.o[s.cur];
-    a.obst = s.obst;
-    a.plane = s.plane;
-    a.pitch = s.pitch;
-    a.w = s.w;
-    a.h = s.h;
-    a.sp = (int)round_up(s.w, 4);
-    a.obst_pressure = p.density * (1.f / 3.f);
-    return a;
-}
-
-// u_x, u_y, |u|, pressure of the current lattice (lbm_fields.hip) into planar
-// host arrays: float[ny][nx] with each sub-domain at its rectangle, or (local)
-// the sub-domains' float[h][w] blocks packed in lbm_local_rects order.  A
-// NULL field is neither computed nor staged.
-void lbm_handle::store_fields(float *ux, float *uy, float *speed, float *pressure, bool local) {
-    if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to derive fields from");
-    float *const host[4] = {ux, uy, speed, pressure};
-    int want = 0;
-    for (float *f : host) want += f ? 1 : 0;
-    if (want == 0) return;
-    sync_all();
-    prof_drop();
-    size_t packed = 0;  // local: cells of the sub-domains before this one
-    for (auto &s : subs) {
-        set_device(s);
-        FieldsArgs a = fields_args(s);
-        const size_t field_floats = (size_t)a.sp * s.h;
-        float *stage = nullptr;
-        HIP_CHECK(hipMalloc(&stage, sizeof(float) * field_floats * want));
-        try {
-            float **dev[4] = {&a.ux, &a.uy, &a.speed, &a.pressure};
-            for (int i = 0, n = 0; i < 4; ++i)
-                if (host[i]) *dev[i] = stage + field_floats * n++;
-            timed(s, s.s_comp, "macroscopic_fields",
-                  [&] { HIP_CHECK(launch_macroscopic_fields(a, false, s.s_comp)); });
-            HIP_CHECK(hipStreamSynchronize(s.s_comp));
-            const size_t off = local ? packed : (size_t)s.rect.y0 * p.nx + s.rect.x0;
-            const size_t pitch = sizeof(float) * (size_t)(local ? s.w : p.nx);
-            for (int i = 0; i < 4; ++i)
-                if (host[i])
-                    HIP_CHECK(hipMemcpy2D(host[i] + off, pitch, *dev[i], sizeof(float) * (size_t)a.sp,
-                                          sizeof(float) * (size_t)s.w, (size_t)s.h, hipMemcpyDeviceToHost));
-        } catch (...) {
-            (void)hipFree(stage);
-            throw;
-        }
-        HIP_CHECK(hipFree(stage));
-        packed += (size_t)s.w * s.h;
-    }
-    prof_collect();
-}
-
-// Total mass (fp64 sum of every local cell's fp32 density) and the largest
-// |u| over the local fluid cells.  The kernel leaves per-block partials;
-// they are folded here in block order, sub-domain after sub-domain, so the
-// same lattice always gives the same bits.
-void lbm_handle::field_stats(double *mass, float *max_speed) {
-    if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to take statistics of");
-    if (!mass && !max_speed) return;
-    sync_all();
-    prof_drop();
-    double total = 0.0;
-    float umax = 0.f;
-    for (auto &s : subs) {
-        set_device(s);
-        FieldsArgs a = fields_args(s);
-        const int nb = fields_blocks(s.w, s.h);
-        // [nb doubles | nb floats]
-        void *part = nullptr;
-        HIP_CHECK(hipMalloc(&part, (sizeof(double) + sizeof(float)) * (size_t)nb));
-        std::vector<double> host((size_t)nb + ((size_t)nb + 1) / 2);  // the same block: doubles, then floats
-        try {
-            a.mass_part = static_cast<double *>(part);
-            a.umax_part = reinterpret_cast<float *>(a.mass_part + nb);
-            timed(s, s.s_comp, "macroscopic_fields stats", [&] { HIP_CHECK(launch_macroscopic_fields(a, true, s.s_comp)); });
-            HIP_CHECK(hipStreamSynchronize(s.s_comp));
-            HIP_CHECK(hipMemcpy(host.data(), part, (sizeof(double) + sizeof(float)) * (size_t)nb, hipMemcpyDeviceToHost));
-        } catch (...) {
-            (void)hipFree(part);
-            throw;
-        }
-        HIP_CHECK(hipFree(part));
-        std::vector<float> hu((size_t)nb);
-        memcpy(hu.data(), host.data() + nb, sizeof(float) * (size_t)nb);
-        for (int b = 0; b < nb; ++b) {
-            total += host[(size_t)b];
-            umax = std::max(umax, hu[(size_t)b]);
-        }
-    }
-    prof_collect();
-    if (mass) *mass = total;
-    if (max_speed) *max_speed = umax;
 }
 
 void lbm_handle::destroy() {

@@ -3,7 +3,7 @@
 //   lbm_engine.hip        create, allocation, placement probe, the step loop,
 //                         load / store / destroy (the run path);
 //   lbm_fields.hip        macroscopic fields and lattice stats of the current
-//                         lattice (kernel; its host side is in lbm_engine.hip);
+//                         lattice (kernel and its host side);
 //   lbm_forces.hip        momentum-exchange wall forces of the current lattice
 //                         (wall list, kernels and their host side);
 //   lbm_exchange.hip      partition rule, torus neighbours, halo destinations,
@@ -55,6 +55,7 @@
 #include <array>
 #include <vector>
 
+#include "lbm_common.hpp"
 #include "lbm_hip.h"
 #include "lbm_layout.hpp"
 
@@ -96,24 +97,6 @@ struct State;  // wall lists of a handle that asked for wall forces (lbm_forces.
 
 namespace lbm {
 namespace eng {
-
-struct lbm_failure : std::runtime_error {
-    int code;
-    lbm_failure(int c, const std::string &m) : std::runtime_error(m), code(c) {}
-};
-
-#define HIP_CHECK(expr)                                                                                  \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess)                                                                            \
-            throw lbm_failure(LBM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));             \
-    } while (0)
-
-#define NCCL_CHECK(expr)                                                                                 \
-    do {                                                                                                 \
-        ncclResult_t r_ = (expr);                                                                        \
-        if (r_ != ncclSuccess) throw lbm_failure(LBM_E_RCCL, std::string(#expr) + ": " + ncclGetErrorString(r_)); \
-    } while (0)
 
 inline long long round_up(long long v, long long m) { return (v + m - 1) / m * m; }
 

@@ -2,7 +2,8 @@
 // (lbm_store_fields / lbm_field_stats): u_x, u_y, |u| and pressure of the
 // current SoA lattice, exactly as lbmhost::macroscopic (host/lbm_host.hpp;
 // writeResults, LatticeBoltzmannUtils.hpp:221-281) derives them from the AoS
-// cells, without moving the nine populations to the host.
+// cells, without moving the nine populations to the host.  The kernel, then
+// the D2Q9 engine's host side.
 //
 // Memory-bound: 37 B read (nine populations + the obstacle byte) and at most
 // 16 B written per cell, no reuse, no LDS staging.  One lane takes four
@@ -19,7 +20,7 @@
 
 #include <algorithm>
 
-#include "lbm_layout.hpp"
+#include "lbm_engine.hpp"
 
 namespace lbm {
 
@@ -175,3 +176,87 @@ hipError_t launch_macroscopic_fields(const FieldsArgs &a, bool stats, hipStream_
 }
 
 }  // namespace lbm
+
+// ---- D2Q9 engine: host side ----
+
+FieldsArgs lbm_handle::fields_args(const Sub &s) const {
+    FieldsArgs a{};
+    a.o = s.o[s.cur];
+    a.obst = s.obst;
+    a.plane = s.plane;
+    a.pitch = s.pitch;
+    a.w = s.w;
+    a.h = s.h;
+    a.sp = (int)round_up(s.w, 4);
+    a.obst_pressure = p.density * (1.f / 3.f);
+    return a;
+}
+
+// u_x, u_y, |u|, pressure of the current lattice into planar
+// host arrays: float[ny][nx] with each sub-domain at its rectangle, or (local)
+// the sub-domains' float[h][w] blocks packed in lbm_local_rects order.  A
+// NULL field is neither computed nor staged.
+void lbm_handle::store_fields(float *ux, float *uy, float *speed, float *pressure, bool local) {
+    if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to derive fields from");
+    float *const host[4] = {ux, uy, speed, pressure};
+    int want = 0;
+    for (float *f : host) want += f ? 1 : 0;
+    if (want == 0) return;
+    sync_all();
+    prof_drop();
+    size_t packed = 0;  // local: cells of the sub-domains before this one
+    for (auto &s : subs) {
+        set_device(s);
+        FieldsArgs a = fields_args(s);
+        const size_t field_floats = (size_t)a.sp * s.h;
+        const DeviceStage stage(sizeof(float) * field_floats * want);
+        float **dev[4] = {&a.ux, &a.uy, &a.speed, &a.pressure};
+        for (int i = 0, n = 0; i < 4; ++i)
+            if (host[i]) *dev[i] = stage.as<float>() + field_floats * n++;
+        timed(s, s.s_comp, "macroscopic_fields", [&] { HIP_CHECK(launch_macroscopic_fields(a, false, s.s_comp)); });
+        HIP_CHECK(hipStreamSynchronize(s.s_comp));
+        const size_t off = local ? packed : (size_t)s.rect.y0 * p.nx + s.rect.x0;
+        const size_t pitch = sizeof(float) * (size_t)(local ? s.w : p.nx);
+        for (int i = 0; i < 4; ++i)
+            if (host[i])
+                HIP_CHECK(hipMemcpy2D(host[i] + off, pitch, *dev[i], sizeof(float) * (size_t)a.sp,
+                                      sizeof(float) * (size_t)s.w, (size_t)s.h, hipMemcpyDeviceToHost));
+        packed += (size_t)s.w * s.h;
+    }
+    prof_collect();
+}
+
+// Total mass (fp64 sum of every local cell's fp32 density) and the largest
+// |u| over the local fluid cells.  The kernel leaves per-block partials;
+// they are folded here in block order, sub-domain after sub-domain, so the
+// same lattice always gives the same bits.
+void lbm_handle::field_stats(double *mass, float *max_speed) {
+    if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to take statistics of");
+    if (!mass && !max_speed) return;
+    sync_all();
+    prof_drop();
+    double total = 0.0;
+    float umax = 0.f;
+    for (auto &s : subs) {
+        set_device(s);
+        FieldsArgs a = fields_args(s);
+        const int nb = fields_blocks(s.w, s.h);
+        // [nb doubles | nb floats]
+        const DeviceStage part((sizeof(double) + sizeof(float)) * (size_t)nb);
+        std::vector<double> host((size_t)nb + ((size_t)nb + 1) / 2);  // the same block: doubles, then floats
+        a.mass_part = part.as<double>();
+        a.umax_part = reinterpret_cast<float *>(a.mass_part + nb);
+        timed(s, s.s_comp, "macroscopic_fields stats", [&] { HIP_CHECK(launch_macroscopic_fields(a, true, s.s_comp)); });
+        HIP_CHECK(hipStreamSynchronize(s.s_comp));
+        HIP_CHECK(hipMemcpy(host.data(), part.get(), (sizeof(double) + sizeof(float)) * (size_t)nb, hipMemcpyDeviceToHost));
+        std::vector<float> hu((size_t)nb);
+        memcpy(hu.data(), host.data() + nb, sizeof(float) * (size_t)nb);
+        for (int b = 0; b < nb; ++b) {
+            total += host[(size_t)b];
+            umax = std::max(umax, hu[(size_t)b]);
+        }
+    }
+    prof_collect();
+    if (mass) *mass = total;
+    if (max_speed) *max_speed = umax;
+}

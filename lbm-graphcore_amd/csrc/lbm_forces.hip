@@ -299,26 +299,19 @@ void lbm_handle::store_wall_force(float *fx, float *fy) {
         const WallList &wl = forces->lists[k];
         WallArgs a = wl.args(s.o[s.cur], s.plane);
         const size_t field_floats = (size_t)s.w * s.h;
-        float *stage = nullptr;
-        HIP_CHECK(hipMalloc(&stage, sizeof(float) * field_floats * want));
-        try {
-            HIP_CHECK(hipMemsetAsync(stage, 0, sizeof(float) * field_floats * want, s.s_comp));
-            float **dev[2] = {&a.mx, &a.my};
-            for (int i = 0, n = 0; i < 2; ++i)
-                if (host[i]) *dev[i] = stage + field_floats * n++;
-            if (wl.n > 0)
-                timed(s, s.s_comp, "wall_force map", [&] { HIP_CHECK(wl.launch(lbm::forces::WALL_MAP, a, s.s_comp)); });
-            HIP_CHECK(hipStreamSynchronize(s.s_comp));
-            const size_t off = (size_t)s.rect.y0 * p.nx + s.rect.x0;
-            for (int i = 0; i < 2; ++i)
-                if (host[i])
-                    HIP_CHECK(hipMemcpy2D(host[i] + off, sizeof(float) * (size_t)p.nx, *dev[i], sizeof(float) * (size_t)s.w,
-                                          sizeof(float) * (size_t)s.w, (size_t)s.h, hipMemcpyDeviceToHost));
-        } catch (...) {
-            (void)hipFree(stage);
-            throw;
-        }
-        HIP_CHECK(hipFree(stage));
+        const DeviceStage stage(sizeof(float) * field_floats * want);
+        HIP_CHECK(hipMemsetAsync(stage.get(), 0, sizeof(float) * field_floats * want, s.s_comp));
+        float **dev[2] = {&a.mx, &a.my};
+        for (int i = 0, n = 0; i < 2; ++i)
+            if (host[i]) *dev[i] = stage.as<float>() + field_floats * n++;
+        if (wl.n > 0)
+            timed(s, s.s_comp, "wall_force map", [&] { HIP_CHECK(wl.launch(lbm::forces::WALL_MAP, a, s.s_comp)); });
+        HIP_CHECK(hipStreamSynchronize(s.s_comp));
+        const size_t off = (size_t)s.rect.y0 * p.nx + s.rect.x0;
+        for (int i = 0; i < 2; ++i)
+            if (host[i])
+                HIP_CHECK(hipMemcpy2D(host[i] + off, sizeof(float) * (size_t)p.nx, *dev[i], sizeof(float) * (size_t)s.w,
+                                      sizeof(float) * (size_t)s.w, (size_t)s.h, hipMemcpyDeviceToHost));
     }
     prof_collect();
 }

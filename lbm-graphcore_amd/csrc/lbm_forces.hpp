@@ -1,6 +1,6 @@
 // lbm_forces.hpp -- wall list and kernels of the momentum-exchange wall forces
 // (include/lbm_forces_hip.h), shared by the D2Q9 engine (lbm_forces.hip) and
-// the D3Q19 engine (lbm3d_forces.hip, lbm3d.hip).
+// the D3Q19 engine (lbm3d_forces.hip).
 //
 // Only wall cells (blocked cells with a fluid neighbour) carry force, so the
 // hot path is a gather over a compact list: per wall cell the offset of its

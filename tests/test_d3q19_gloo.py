@@ -1,6 +1,6 @@
 """D3Q19 z-slab decomposition on the CPU (gloo, world_size 2, 3 and 4).
 
-Mirrors the engine's multi-rank D3Q19 path (lbm-graphcore_amd/csrc/lbm3d.hip):
+Mirrors the engine's multi-rank D3Q19 path (lbm-graphcore_amd/csrc/lbm3d_engine.hip):
 round-robin z extents, and after every step each rank sends its top plane's
 speeds 9..13 (c_z = +1, one contiguous block) up and its bottom plane's speeds
 14..18 down, posted in the same order as the RCCL group (send up, send down,

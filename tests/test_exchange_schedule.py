@@ -4,7 +4,7 @@
 RCCL matches the messages between two ranks purely by the order in which each
 posts them inside one ncclGroupStart/End.  lbm_exchange_schedule /
 lbm3d_exchange_schedule export the exact list the engines post
-(lbm_engine.hip exchange_posts, lbm3d.hip slab_posts -- the RCCL exchange
+(lbm_engine.hip exchange_posts, lbm3d_abi.hip slab_posts -- the RCCL exchange
 loops iterate these same lists).  Here every rank's list is generated and
 paired the way RCCL pairs it: the k-th send from a to b with the k-th receive
 b posts from a.  Each pair must carry the same number of floats, the receive
