@@ -1,9 +1,10 @@
 // lbm3d_abi.hip -- the extern "C" functions of include/lbm3d_hip.h,
 // include/lbm3d_fields_hip.h and the D3Q19 functions of
-// include/lbm_forces_hip.h over the engine (lbm3d_engine.hpp), and the
-// posting order of its RCCL ghost exchange.
+// include/lbm_forces_hip.h and include/lbm_averages_hip.h over the engine
+// (lbm3d_engine.hpp), and the posting order of its RCCL ghost exchange.
 
 #include "lbm3d_engine.hpp"
+#include "lbm_averages_hip.h"
 
 namespace lbm {
 std::array<lbm_xfer, 4> slab_posts(int rank, int world, long long floats) {
@@ -96,6 +97,36 @@ int lbm3d_set_bodies(lbm3d_handle *h, const int32_t *labels, int32_t nbodies) {
 int lbm3d_body_forces(lbm3d_handle *h, double *fx, double *fy, double *fz, int64_t *links, int32_t nbodies) {
     if (!h) return LBM_E_INVALID;
     return guarded(h, [&] { h->body_forces(fx, fy, fz, links, nbodies); });
+}
+
+int lbm3d_avg_begin(lbm3d_handle *h, int32_t moments) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->avg_begin(moments); });
+}
+
+int lbm3d_avg_sample(lbm3d_handle *h) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->avg_sample(); });
+}
+
+int lbm3d_avg_samples(lbm3d_handle *h, int64_t *n) {
+    if (!h || !n) return LBM_E_INVALID;
+    return guarded(h, [&] { *n = h->avg_samples(); });
+}
+
+int lbm3d_avg_store_sums(lbm3d_handle *h, double *const out[LBM3D_AVG_FIELDS]) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->avg_store_sums(out); });
+}
+
+int lbm3d_avg_store(lbm3d_handle *h, float *const out[LBM3D_AVG_FIELDS]) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->avg_store(out); });
+}
+
+int lbm3d_avg_end(lbm3d_handle *h) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->avg_end(); });
 }
 
 int lbm3d_last_run_seconds(lbm3d_handle *h, double *seconds) {

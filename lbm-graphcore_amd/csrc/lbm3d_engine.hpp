@@ -6,6 +6,7 @@
 //                      step loop, ghost exchange, load / store / destroy;
 //   lbm3d_fields.hip   macroscopic fields and lattice stats (kernel + host side);
 //   lbm3d_forces.hip   momentum-exchange wall forces (kernels + host side);
+//   lbm3d_averages.hip time-averaged fields and Reynolds stresses (kernels + host side);
 //   lbm3d_abi.hip      the extern "C" functions and the RCCL posting order.
 #pragma once
 
@@ -24,6 +25,10 @@
 #include "lbm_forces_hip.h"
 
 namespace lbm {
+
+namespace avg {
+struct State;  // accumulators of a handle that is averaging (lbm_moments.hpp)
+}
 
 constexpr int Q3 = 19;
 constexpr int GZ3 = 3;  // ghost planes each side of every slab lattice (and obst_g)
@@ -220,4 +225,12 @@ struct lbm3d_handle {
     void store_wall_force(float *const (&host)[3]);
     void set_bodies(const int32_t *labels, int32_t nbodies);
     void body_forces(double *fx, double *fy, double *fz, int64_t *links, int32_t nbodies);
+    // lbm3d_averages.hip (include/lbm_averages_hip.h)
+    lbm::avg::State *averages = nullptr;  // set between avg_begin and avg_end
+    void avg_begin(int moments);
+    void avg_sample();
+    int64_t avg_samples() const;
+    void avg_store_sums(double *const *out);
+    void avg_store(float *const *out);
+    void avg_end();
 };

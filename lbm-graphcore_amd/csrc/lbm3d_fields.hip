@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "lbm3d_cell_macro.hpp"
 #include "lbm3d_engine.hpp"
 
 namespace lbm {
@@ -35,29 +36,6 @@ constexpr int F3Q = 19;
 constexpr int F3X = 64, F3Y = 4;  // block: 64 lanes along x (one wave) x 4 rows
 // blocks a launch aims for (planes beyond are strided over): bounds the partials the host folds per slab
 constexpr int F3_TARGET_BLOCKS = 16384;
-
-struct Cell3Macro {
-    float ux, uy, uz, u, pressure;
-};
-
-// NEED_V: a velocity component or |u| wanted (three divides); NEED_U: |u| wanted (sqrt); rho is always formed
-template <bool NEED_V, bool NEED_U>
-__device__ __forceinline__ Cell3Macro cell3_macro(const float (&s)[F3Q], bool blocked, float obst_pressure,
-                                                  float &rho) {
-    rho = s[0];
-#pragma unroll
-    for (int k = 1; k < F3Q; ++k) rho += s[k];
-    Cell3Macro m{0.f, 0.f, 0.f, 0.f, obst_pressure};
-    if (blocked) return m;
-    if (NEED_V) {
-        m.ux = ((s[1] + s[5] + s[7] + s[10] + s[16]) - (s[2] + s[6] + s[8] + s[11] + s[15])) / rho;
-        m.uy = ((s[3] + s[5] + s[8] + s[12] + s[18]) - (s[4] + s[6] + s[7] + s[13] + s[17])) / rho;
-        m.uz = ((s[9] + s[10] + s[11] + s[12] + s[13]) - (s[14] + s[15] + s[16] + s[17] + s[18])) / rho;
-    }
-    if (NEED_U) m.u = sqrtf(m.ux * m.ux + m.uy * m.uy + m.uz * m.uz);
-    m.pressure = rho * (1.f / 3.f);
-    return m;
-}
 
 __device__ __forceinline__ Cell3Macro cell3_dispatch(const float (&s)[F3Q], bool blocked, float obst_pressure,
                                                      bool want_v, bool want_u, float &rho) {

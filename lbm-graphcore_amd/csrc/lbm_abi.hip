@@ -1,6 +1,8 @@
 // lbm_abi.hip -- the extern "C" functions of include/lbm_hip.h and the D2Q9
-// functions of include/lbm_forces_hip.h over the engine.
+// functions of include/lbm_forces_hip.h and include/lbm_averages_hip.h over
+// the engine.
 
+#include "lbm_averages_hip.h"
 #include "lbm_engine.hpp"
 #include "lbm_forces_hip.h"
 
@@ -182,6 +184,36 @@ int lbm_set_bodies(lbm_handle *h, const int32_t *labels, int32_t nbodies) {
 int lbm_body_forces(lbm_handle *h, double *fx, double *fy, int64_t *links, int32_t nbodies) {
     if (!h) return LBM_E_INVALID;
     return guarded(h, [&] { h->body_forces(fx, fy, links, nbodies); });
+}
+
+int lbm_avg_begin(lbm_handle *h, int32_t moments) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->avg_begin(moments); });
+}
+
+int lbm_avg_sample(lbm_handle *h) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->avg_sample(); });
+}
+
+int lbm_avg_samples(lbm_handle *h, int64_t *n) {
+    if (!h || !n) return LBM_E_INVALID;
+    return guarded(h, [&] { *n = h->avg_samples(); });
+}
+
+int lbm_avg_store_sums(lbm_handle *h, double *const out[LBM_AVG_FIELDS]) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->avg_store_sums(out); });
+}
+
+int lbm_avg_store(lbm_handle *h, float *const out[LBM_AVG_FIELDS]) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->avg_store(out); });
+}
+
+int lbm_avg_end(lbm_handle *h) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->avg_end(); });
 }
 
 int64_t lbm_local_cells(lbm_handle *h) {

@@ -927,6 +927,7 @@ void lbm_handle::destroy() {
     drop_graphs();
     prof_release();
     forces_release();
+    avg_end();
     for (auto &s : subs) {
         if (hipSetDevice(s.dev) != hipSuccess) continue;
         (void)hipDeviceSynchronize();

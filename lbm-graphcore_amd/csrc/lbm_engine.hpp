@@ -6,6 +6,8 @@
 //                         lattice (kernel and its host side);
 //   lbm_forces.hip        momentum-exchange wall forces of the current lattice
 //                         (wall list, kernels and their host side);
+//   lbm_averages.hip      time-averaged fields and Reynolds stresses: fp64
+//                         sums beside the lattice (kernels and their host side);
 //   lbm_exchange.hip      partition rule, torus neighbours, halo destinations,
 //                         the posted exchange (RCCL or device copies);
 //   lbm_split.hip         work decomposition: boundary / interior split,
@@ -92,6 +94,9 @@ hipError_t launch_resident_reduce(const float *partials, float *av_local, int st
 hipError_t launch_debug_spin(int microseconds, hipStream_t s);
 namespace forces {
 struct State;  // wall lists of a handle that asked for wall forces (lbm_forces.hip)
+}
+namespace avg {
+struct State;  // accumulators of a handle that is averaging (lbm_moments.hpp)
 }
 }  // namespace lbm
 
@@ -400,5 +405,13 @@ struct lbm_handle {
     void store_wall_force(float *fx, float *fy);
     void set_bodies(const int32_t *labels, int32_t nbodies);
     void body_forces(double *fx, double *fy, int64_t *links, int32_t nbodies);
+    // time-averaged fields (lbm_averages.hip; include/lbm_averages_hip.h)
+    lbm::avg::State *averages = nullptr;  // set between avg_begin and avg_end
+    void avg_begin(int moments);
+    void avg_sample();
+    int64_t avg_samples() const;
+    void avg_store_sums(double *const *out);
+    void avg_store(float *const *out);
+    void avg_end();
     void destroy();
 };

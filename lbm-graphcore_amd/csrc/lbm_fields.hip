@@ -20,6 +20,7 @@
 
 #include <algorithm>
 
+#include "lbm_cell_macro.hpp"
 #include "lbm_engine.hpp"
 
 namespace lbm {
@@ -28,27 +29,6 @@ namespace {
 
 // most blocks of a launch (grid-stride beyond): also the most partials the host folds per sub-domain
 constexpr int FIELDS_MAX_BLOCKS = 8192;
-
-struct CellMacro {
-    float ux, uy, u, pressure;
-};
-
-// need_v: u_x / u_y wanted (two divides); need_u: |u| wanted (sqrt); rho is always formed
-template <bool NEED_V, bool NEED_U>
-__device__ __forceinline__ CellMacro cell_macro(const float (&c)[Q], bool blocked, float obst_pressure, float &rho) {
-    rho = 0.f;
-#pragma unroll
-    for (int k = 0; k < Q; ++k) rho += c[k];
-    CellMacro m{0.f, 0.f, 0.f, obst_pressure};
-    if (blocked) return m;
-    if (NEED_V) {
-        m.ux = (c[1] + c[5] + c[8] - (c[3] + c[6] + c[7])) / rho;
-        m.uy = (c[2] + c[5] + c[6] - (c[4] + c[7] + c[8])) / rho;
-    }
-    if (NEED_U) m.u = sqrtf((m.ux * m.ux) + (m.uy * m.uy));
-    m.pressure = rho * (1.f / 3.f);
-    return m;
-}
 
 }  // namespace
 

@@ -9,6 +9,8 @@
 //   writeAverageVelocities  LatticeBoltzmannUtils.hpp:208-219
 //   writeResults            LatticeBoltzmannUtils.hpp:221-281
 //   writeResultsFromFields  the same file from lbm_store_fields' planar arrays
+//   writeMeanState          the time averages of lbm_avg_store in the same row
+//                           format (lbm_runner --mean-every; no reference counterpart)
 //   averageVelocity         LastChance.cpp:290-339 (used by compare_lbm)
 //   labelBodies, wallForces, writeForces
 //                           the momentum-exchange wall forces of
@@ -156,10 +158,17 @@ inline bool writeAverageVelocities(const std::string &filename, const std::vecto
     return true;
 }
 
+// one row of a per-cell .dat file: `ii jj v[0] .. v[n-1] obstacle`
+inline void writeCellRow(std::ostream &file, size_t ii, size_t jj, const float *v, int n, bool obstacle) {
+    file << ii << " " << jj << std::setprecision(12) << std::scientific;
+    for (int k = 0; k < n; ++k) file << " " << v[k];
+    file << " " << (int)obstacle << "\n";
+}
+
 // one final_state.dat row: `ii jj u_x u_y |u| pressure obstacle`
 inline void writeResultsRow(std::ostream &file, size_t ii, size_t jj, const Macro &m, bool obstacle) {
-    file << ii << " " << jj << " " << std::setprecision(12) << std::scientific << m.ux << " " << m.uy << " " << m.u
-         << " " << m.pressure << " " << (int)obstacle << "\n";
+    const float v[4] = {m.ux, m.uy, m.u, m.pressure};
+    writeCellRow(file, ii, jj, v, 4, obstacle);
 }
 
 inline bool writeResults(const std::string &filename, const Params &p, const Obstacles &o,
@@ -265,6 +274,25 @@ inline BodyForces wallForces(const Params &p, const Obstacles &o, const std::vec
             }
         }
     return r;
+}
+
+// mean_state.dat from the seven planar float[ny][nx] arrays of lbm_avg_store
+// (LBM_AVG_* order): `ii jj mean_ux mean_uy mean_pressure c_uxux c_uxuy c_uyuy
+// c_pp obstacle`, through the row formatter of final_state.dat
+inline bool writeMeanState(const std::string &filename, const Params &p, const Obstacles &o,
+                           const std::vector<float> (&f)[7]) {
+    const size_t n = p.nx * p.ny;
+    for (const auto &a : f)
+        if (a.size() != n) return false;
+    std::ofstream file(filename);
+    if (!file.is_open()) return false;
+    for (size_t jj = 0; jj < p.ny; ++jj)
+        for (size_t ii = 0; ii < p.nx; ++ii) {
+            const size_t i = ii + jj * p.nx;
+            const float v[7] = {f[0][i], f[1][i], f[2][i], f[3][i], f[4][i], f[5][i], f[6][i]};
+            writeCellRow(file, ii, jj, v, 7, o.at(ii, jj));
+        }
+    return true;
 }
 
 // forces.dat: `body fx fy links` per body, then `total fx fy links`

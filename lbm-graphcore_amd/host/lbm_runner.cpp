@@ -3,7 +3,7 @@
 //
 //   lbm_runner --params P --obstacles O [-n N] [--device gpu|loopback|cpu] [-d] [--exe ignored]
 //              [--runs 5] [--kernel auto|resident|stream|step2|vec4|scalar|pipeline] [--spl S] [--out-dir DIR]
-//              [--tolerance] [--device-fields] [--forces] [--json FILE]
+//              [--tolerance] [--device-fields] [--forces] [--mean-every N] [--json FILE]
 //
 // Flow (same program numbering as the reference):
 //   load params/obstacles -> initialise cells on host -> create engine
@@ -23,12 +23,19 @@
 // = 8-connected periodic components), one `body fx fy links` line per body and
 // a final `total` line -- through lbm_set_bodies / lbm_body_forces /
 // lbm_wall_force on the GPU, through lbmhost::wallForces with --device cpu.
+// --mean-every N runs the first run as lbm_run_steps chunks of N steps (the
+// remainder last, the accelerate with the first), samples the time averages
+// after each chunk (lbm_averages_hip.h) and writes mean_state.dat after the
+// run: `x y mean_ux mean_uy mean_pressure c_uxux c_uxuy c_uyuy c_pp obstacle`
+// per cell in final_state.dat's row format; av_vels.dat and final_state.dat
+// are the plain run's.
 // --device loopback places all N sub-domains on GPU 0 (the emulator analogue
 // of --device ipumodel: exercises the multi-GPU halo path on one device).
 // --device cpu runs the same fused step on the host's cores (lbm_cpu.hpp:
 // OpenMP rows, bitwise equal to the GPU engine's default numerics); the
-// GPU-only options (-n, --tolerance, --kernel, --spl, --graph-steps, --device-fields) do not
+// GPU-only options (-n, --tolerance, --kernel, --spl, --graph-steps, --device-fields, --mean-every) do not
 // apply there and are refused with a message.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -39,6 +46,7 @@
 #include <string>
 #include <vector>
 
+#include "lbm_averages_hip.h"
 #include "lbm_cpu.hpp"
 #include "lbm_forces_hip.h"
 #include "lbm_host.hpp"
@@ -65,6 +73,9 @@ void usage(const char *exe) {
               << "                       |u|, pressure; 16 B per cell to the host instead of 36); same bytes in the file\n"
               << "      --forces         also write forces.dat: drag / lift per obstacle body (momentum exchange of the\n"
               << "                       last step) and their total\n"
+              << "      --mean-every arg also write mean_state.dat: time means of u_x, u_y, pressure and their central\n"
+              << "                       second moments (Reynolds stresses, pressure variance), sampled on the device\n"
+              << "                       every arg steps\n"
               << "      --out-dir arg    directory for av_vels.dat / final_state.dat (default: .)\n"
               << "      --graph-steps arg  replay the step loop as hipGraphs of 2*arg launches (0 = library default, <0 = off)\n"
               << "      --dump-partitioning arg  write the sub-domain decomposition as JSON\n"
@@ -137,7 +148,7 @@ int main(int argc, char *argv[]) {
     std::string paramsFile, obstaclesFile, device = "gpu", exeFile, kernel = "auto", outDir = ".", dumpFile, jsonFile;
     std::vector<std::string> gpuOnly;  // GPU-only options given on the command line
     int spl = 0;
-    int numGpus = 1, runs = 5, graphSteps = 0;
+    int numGpus = 1, runs = 5, graphSteps = 0, meanEvery = 0;
     bool debug = false, tolerance = false, deviceFields = false, forces = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -191,6 +202,11 @@ int main(int argc, char *argv[]) {
             gpuOnly.push_back(a);
         } else if (a == "--forces") {
             forces = true;
+        } else if (a == "--mean-every") {
+            if (!next(v)) { usage(argv[0]); return EXIT_FAILURE; }
+            meanEvery = std::atoi(v.c_str());
+            if (meanEvery < 1) { usage(argv[0]); return EXIT_FAILURE; }
+            gpuOnly.push_back(a);
         } else if (a == "--out-dir") {
             if (!next(outDir)) { usage(argv[0]); return EXIT_FAILURE; }
         } else if (a == "--graph-steps") {
@@ -317,18 +333,45 @@ int main(int argc, char *argv[]) {
     lbmhost::timedStep("Running copy to device step", [&]() {
         lbmhost::check(lbm_load_cells(h, cells.data()), h, "lbm_load_cells");
     });
-    total_compute_time += lbmhost::timedStep("Running LBM", [&]() { lbmhost::check(lbm_run(h), h, "lbm_run"); });
+    if (meanEvery > 0) {
+        total_compute_time += lbmhost::timedStep("Running LBM", [&]() {
+            lbmhost::check(lbm_avg_begin(h, LBM_AVG_MEAN | LBM_AVG_SECOND), h, "lbm_avg_begin");
+            for (int done = 0; done < (int)params->maxIters;) {
+                const int n = std::min(meanEvery, (int)params->maxIters - done);
+                lbmhost::check(lbm_run_steps(h, n, done == 0), h, "lbm_run_steps");
+                lbmhost::check(lbm_store(h, nullptr, av_vels.data() + done, n), h, "lbm_store");
+                lbmhost::check(lbm_avg_sample(h), h, "lbm_avg_sample");
+                done += n;
+            }
+        });
+    } else {
+        total_compute_time += lbmhost::timedStep("Running LBM", [&]() { lbmhost::check(lbm_run(h), h, "lbm_run"); });
+    }
+    std::vector<float> means[LBM_AVG_FIELDS];         // --mean-every: mean_state.dat's columns, planar
+    // --mean-every gathered av_vels per chunk: the last run's would overwrite them
+    float *const avOut = meanEvery > 0 ? nullptr : av_vels.data();
     std::vector<float> f_ux, f_uy, f_u, f_pressure;  // --device-fields: final_state.dat's columns, planar
     lbmhost::BodyForces bodyForces;                   // --forces: forces.dat
     lbmhost::timedStep("Running copy to host step", [&]() {
         if (deviceFields) {
             const size_t n = params->nx * params->ny;
             for (auto *f : {&f_ux, &f_uy, &f_u, &f_pressure}) f->assign(n, 0.f);
-            lbmhost::check(lbm_store(h, nullptr, av_vels.data(), (int32_t)av_vels.size()), h, "lbm_store");
+            if (avOut) lbmhost::check(lbm_store(h, nullptr, avOut, (int32_t)av_vels.size()), h, "lbm_store");
             lbmhost::check(lbm_store_fields(h, f_ux.data(), f_uy.data(), f_u.data(), f_pressure.data()), h,
                            "lbm_store_fields");
         } else {
-            lbmhost::check(lbm_store(h, cells.data(), av_vels.data(), (int32_t)av_vels.size()), h, "lbm_store");
+            lbmhost::check(lbm_store(h, cells.data(), avOut, (int32_t)av_vels.size()), h, "lbm_store");
+        }
+        int64_t samples = 0;
+        if (meanEvery > 0) lbmhost::check(lbm_avg_samples(h, &samples), h, "lbm_avg_samples");
+        if (samples > 0) {
+            float *out[LBM_AVG_FIELDS];
+            for (int f = 0; f < LBM_AVG_FIELDS; ++f) {
+                means[f].assign(params->nx * params->ny, 0.f);
+                out[f] = means[f].data();
+            }
+            lbmhost::check(lbm_avg_store(h, out), h, "lbm_avg_store");
+            lbmhost::check(lbm_avg_end(h), h, "lbm_avg_end");
         }
         if (forces) {
             std::vector<int32_t> labels;
@@ -347,6 +390,7 @@ int main(int argc, char *argv[]) {
     });
     lbmhost::timedStep("Writing output files ", [&]() {
         if (forces) lbmhost::writeForces(outDir + "/forces.dat", bodyForces);
+        if (!means[0].empty()) lbmhost::writeMeanState(outDir + "/mean_state.dat", *params, *obstacles, means);
         lbmhost::writeAverageVelocities(outDir + "/av_vels.dat", av_vels);
         if (deviceFields)
             lbmhost::writeResultsFromFields(outDir + "/final_state.dat", *params, *obstacles, f_ux, f_uy, f_u,

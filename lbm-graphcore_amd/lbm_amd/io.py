@@ -301,6 +301,45 @@ def label_bodies(obstacles):
     return labels, int(roots.size)
 
 
+# ---- time averages: the definition of include/lbm_averages_hip.h in numpy ----
+
+def _moment_pairs(nv):
+    """(a, b) of the second-moment sums after the nv + 1 first moments: the velocity
+    pairs u_i u_j (i <= j, i outer), then p p -- the order of the header's enums."""
+    return [(i, j) for i in range(nv) for j in range(i, nv)] + [(nv, nv)]
+
+
+def moment_sums(samples, second: bool = True):
+    """The fp64 sums Engine.avg_sums() returns.  samples: a sequence of samples in time
+    order, each a sequence of float32 arrays (ux, uy[, uz], pressure) as fields() gives
+    them.  Returns the list [S_ux, S_uy, (S_uz,) S_p] and, with `second`, the sums of
+    products in the header's order: S += (double)a, S_ab += (double)a * (double)b."""
+    samples = [[np.asarray(f, np.float32).astype(np.float64) for f in s] for s in samples]
+    first = len(samples[0])
+    pairs = _moment_pairs(first - 1) if second else []
+    sums = [np.zeros(samples[0][0].shape, np.float64) for _ in range(first + len(pairs))]
+    for s in samples:
+        for k in range(first):
+            sums[k] += s[k]
+        for k, (a, b) in enumerate(pairs):
+            sums[first + k] += s[a] * s[b]
+    return sums
+
+
+def moment_means(sums, n: int):
+    """The float32 arrays Engine.mean_fields() returns from the sums of n samples: the
+    means (float)(S_a / n), then (if the sums hold them) the central second moments
+    (float)(S_ab / n - (S_a / n) * (S_b / n)), every operation in fp64 in that order."""
+    sums = [np.asarray(s, np.float64) for s in sums]
+    nv = {3: 2, 7: 2, 4: 3, 11: 3}[len(sums)]
+    first, dn = nv + 1, np.float64(n)
+    out = [(s / dn).astype(np.float32) for s in sums[:first]]
+    if len(sums) > first:
+        for k, (a, b) in enumerate(_moment_pairs(nv)):
+            out.append((sums[first + k] / dn - (sums[a] / dn) * (sums[b] / dn)).astype(np.float32))
+    return out
+
+
 def write_average_velocities(filename: str, av_vels) -> bool:
     """`i:\\t%.12e` per step (iostream scientific, precision 12)."""
     try:

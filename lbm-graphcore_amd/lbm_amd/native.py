@@ -56,6 +56,16 @@ EXPORTED_FORCES = [
     "lbm_wall_force", "lbm_store_wall_force", "lbm_set_bodies", "lbm_body_forces",
     "lbm3d_wall_force", "lbm3d_store_wall_force", "lbm3d_set_bodies", "lbm3d_body_forces",
 ]
+# every symbol include/lbm_averages_hip.h declares (time-averaged fields and Reynolds stresses, both engines)
+EXPORTED_AVERAGES = [
+    "lbm_avg_begin", "lbm_avg_sample", "lbm_avg_samples", "lbm_avg_store_sums", "lbm_avg_store", "lbm_avg_end",
+    "lbm3d_avg_begin", "lbm3d_avg_sample", "lbm3d_avg_samples", "lbm3d_avg_store_sums", "lbm3d_avg_store",
+    "lbm3d_avg_end",
+]
+# index order of the output-pointer arrays (LBM_AVG_* / LBM3D_AVG_*): first moments, then second moments
+AVG_FIELDS = ("ux", "uy", "pressure", "uxux", "uxuy", "uyuy", "pp")
+AVG_FIELDS3D = ("ux", "uy", "uz", "pressure", "uxux", "uxuy", "uxuz", "uyuy", "uyuz", "uzuz", "pp")
+AVG_MEAN, AVG_SECOND = 1, 2
 Q3 = 19
 
 
@@ -206,6 +216,18 @@ def load_library() -> ctypes.CDLL:
         "lbm3d_set_bodies": ([H, i32p, i32], ctypes.c_int),
         "lbm3d_body_forces": ([H, f64p, f64p, f64p, i64p, i32], ctypes.c_int),
         "lbm3d_last_run_seconds": ([H, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+        "lbm_avg_begin": ([H, i32], ctypes.c_int),
+        "lbm_avg_sample": ([H], ctypes.c_int),
+        "lbm_avg_samples": ([H, i64p], ctypes.c_int),
+        "lbm_avg_store_sums": ([H, ctypes.POINTER(f64p)], ctypes.c_int),
+        "lbm_avg_store": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
+        "lbm_avg_end": ([H], ctypes.c_int),
+        "lbm3d_avg_begin": ([H, i32], ctypes.c_int),
+        "lbm3d_avg_sample": ([H], ctypes.c_int),
+        "lbm3d_avg_samples": ([H, i64p], ctypes.c_int),
+        "lbm3d_avg_store_sums": ([H, ctypes.POINTER(f64p)], ctypes.c_int),
+        "lbm3d_avg_store": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
+        "lbm3d_avg_end": ([H], ctypes.c_int),
         "lbm3d_total_free_cells": ([H], i64),
         "lbm3d_local_slabs": ([H, i32p, i32p, i32, i32p], ctypes.c_int),
         "lbm3d_last_error": ([H], ctypes.c_char_p),
@@ -340,10 +362,96 @@ class _WallForces:
         return tuple(a[:n] for a in f) + (links[:n],)
 
 
-class Engine(_WallForces):
+class _Averages:
+    """Engine / Engine3D methods over include/lbm_averages_hip.h; the class sets
+    _FORCE_PREFIX ("lbm_" / "lbm3d_"), _force_shape() and _AVG_FIELDS."""
+
+    def _avg_fn(self, name):
+        return getattr(self._L, self._FORCE_PREFIX + "avg_" + name)
+
+    def _avg_which(self, which):
+        names = self._AVG_FIELDS
+        which = names if which is None else tuple(which)
+        bad = [n for n in which if n not in names]
+        if bad or len(set(which)) != len(which):
+            raise ValueError(f"averaged fields are a subset of {names}, each at most once; got {which}")
+        return which
+
+    def _avg_store(self, fn, which, dtype, ctype):
+        out = {n: np.zeros(self._force_shape(), dtype) for n in which}
+        ptrs = (ctypes.POINTER(ctype) * len(self._AVG_FIELDS))()
+        for i, n in enumerate(self._AVG_FIELDS):
+            if n in out:
+                ptrs[i] = out[n].ctypes.data_as(ctypes.POINTER(ctype))
+        self._check(fn(self._h, ptrs))
+        return out
+
+    def avg_begin(self, second: bool = True) -> None:
+        """Start (or restart, re-zeroed) averaging: one fp64 sum per cell beside the lattice
+        for the first moments (ux, uy[, uz], pressure) and, with `second`, for the velocity
+        products and pressure squared.  8 B x fields x cells of device memory."""
+        self._check(self._avg_fn("begin")(self._h, AVG_MEAN | AVG_SECOND if second else AVG_MEAN))
+        self._avg_second = bool(second)
+
+    def avg_sample(self) -> None:
+        """Add the current lattice to the sums (one kernel; nothing goes to the host)."""
+        self._check(self._avg_fn("sample")(self._h))
+
+    @property
+    def avg_samples(self) -> int:
+        n = ctypes.c_int64()
+        self._check(self._avg_fn("samples")(self._h, ctypes.byref(n)))
+        return n.value
+
+    def avg_end(self) -> None:
+        """Free the accumulators (close() frees them too)."""
+        self._check(self._avg_fn("end")(self._h))
+
+    def _avg_default(self):
+        names = self._AVG_FIELDS
+        return names if getattr(self, "_avg_second", True) else names[:len(self._force_shape()) + 1]
+
+    def avg_sums(self, which=None):
+        """{name: float64 array} of the raw sums (lbm_avg_store_sums): lio.moment_sums of the
+        sampled fields(), bit for bit.  Default: every field begun.  RCCL: only this rank's
+        part is written."""
+        which = self._avg_which(self._avg_default() if which is None else which)
+        return self._avg_store(self._avg_fn("store_sums"), which, np.float64, ctypes.c_double)
+
+    def mean_fields(self, which=None):
+        """{name: float32 array}: the time means of "ux", "uy"[, "uz"], "pressure" and, under
+        the second-moment names ("uxux", "uxuy", ..., "pp"), the central moments
+        <a b> - <a><b> (Reynolds stresses, pressure variance), formed on the device
+        (lbm_avg_store): lio.moment_means of avg_sums(), bit for bit."""
+        which = self._avg_which(self._avg_default() if which is None else which)
+        return self._avg_store(self._avg_fn("store"), which, np.float32, ctypes.c_float)
+
+
+class Engine(_WallForces, _Averages):
     """One lbm_handle: the HIP counterpart of the reference's poplar::Engine."""
 
     _FORCE_PREFIX = "lbm_"
+    _AVG_FIELDS = AVG_FIELDS
+
+    def run_averaged(self, steps: int, every: int, accelerate_first: bool = False):
+        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and
+        avg_sample() after each chunk (avg_begin first).  Returns the float32[steps]
+        concatenation of the chunks' average velocities.  accelerate_first applies to the
+        first chunk only.  In bitwise mode the lattice and av_vels equal those of one
+        run_steps(steps).  In tolerance mode a chunked run differs from an unchunked one
+        in the last bits: the steps of a chunk that do not fill a fused launch run as
+        remainder launches, and remainder launches are bitwise."""
+        steps, every = int(steps), int(every)
+        if steps < 0 or every < 1:
+            raise ValueError("steps >= 0 and every >= 1")
+        av, done = [], 0
+        while done < steps:
+            n = min(every, steps - done)
+            self.run_steps(n, accelerate_first and done == 0)
+            av.append(self.store(cells=False, n_av=n)[1].copy())
+            done += n
+            self.avg_sample()
+        return np.concatenate(av) if av else np.zeros(0, np.float32)
 
     def _force_shape(self):
         return (self.params.ny, self.params.nx)
@@ -571,10 +679,26 @@ class Engine(_WallForces):
             pass
 
 
-class Engine3D(_WallForces):
+class Engine3D(_WallForces, _Averages):
     """One lbm3d_handle: the D3Q19 extension engine (include/lbm3d_hip.h)."""
 
     _FORCE_PREFIX = "lbm3d_"
+    _AVG_FIELDS = AVG_FIELDS3D
+
+    def run_averaged(self, steps: int, every: int) -> None:
+        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and
+        avg_sample() after each chunk (avg_begin first).  In bitwise mode the lattice
+        equals that of one run_steps(steps); in tolerance mode a chunked run differs from
+        an unchunked one in the last bits (remainder launches are bitwise)."""
+        steps, every = int(steps), int(every)
+        if steps < 0 or every < 1:
+            raise ValueError("steps >= 0 and every >= 1")
+        done = 0
+        while done < steps:
+            n = min(every, steps - done)
+            self.run_steps(n)
+            done += n
+            self.avg_sample()
 
     def _force_shape(self):
         return (self.params.nz, self.params.ny, self.params.nx)
