@@ -7,6 +7,7 @@
 //   lbm3d_fields.hip   macroscopic fields and lattice stats (kernel + host side);
 //   lbm3d_forces.hip   momentum-exchange wall forces (kernels + host side);
 //   lbm3d_averages.hip time-averaged fields and Reynolds stresses (kernels + host side);
+//   lbm3d_gradients.hip vorticity, divergence, strain rate and Q (kernel + host side);
 //   lbm3d_abi.hip      the extern "C" functions and the RCCL posting order.
 #pragma once
 
@@ -28,6 +29,9 @@ namespace lbm {
 
 namespace avg {
 struct State;  // accumulators of a handle that is averaging (lbm_moments.hpp)
+}
+namespace grad {
+struct Grad3Args;  // lbm_gradients.hpp
 }
 
 constexpr int Q3 = 19;
@@ -233,4 +237,11 @@ struct lbm3d_handle {
     void avg_store_sums(double *const *out);
     void avg_store(float *const *out);
     void avg_end();
+    // lbm3d_gradients.hip (include/lbm_gradients_hip.h)
+    std::vector<float *> grad_faces;  // per slab: face velocity planes, allocated at the first gradient call
+    int grad_prepare();
+    void grad_release();
+    lbm::grad::Grad3Args grad_args(size_t k, int hp, int x0, int y0, int z0, int bx, int by, int bz) const;
+    void store_gradients_box(const lbm3d_box &b, float *const *host);
+    void gradient_stats(double *sum_w2, double *sum_s2, float *max_w, float *max_div);
 };

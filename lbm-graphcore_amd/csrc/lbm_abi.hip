@@ -1,10 +1,11 @@
 // lbm_abi.hip -- the extern "C" functions of include/lbm_hip.h and the D2Q9
-// functions of include/lbm_forces_hip.h and include/lbm_averages_hip.h over
-// the engine.
+// functions of include/lbm_forces_hip.h, include/lbm_averages_hip.h and
+// include/lbm_gradients_hip.h over the engine.
 
 #include "lbm_averages_hip.h"
 #include "lbm_engine.hpp"
 #include "lbm_forces_hip.h"
+#include "lbm_gradients_hip.h"
 
 // --------------------------------------------------------------------------
 // C ABI
@@ -214,6 +215,21 @@ int lbm_avg_store(lbm_handle *h, float *const out[LBM_AVG_FIELDS]) {
 int lbm_avg_end(lbm_handle *h) {
     if (!h) return LBM_E_INVALID;
     return guarded(h, [&] { h->avg_end(); });
+}
+
+int lbm_store_gradients(lbm_handle *h, float *const out[LBM_GRAD_FIELDS]) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->store_gradients(out); });
+}
+
+int lbm_store_gradients_local(lbm_handle *h, float *const out[LBM_GRAD_FIELDS]) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->store_gradients(out, true); });
+}
+
+int lbm_gradient_stats(lbm_handle *h, double *sum_w2, double *sum_s2, float *max_w, float *max_div) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->gradient_stats(sum_w2, sum_s2, max_w, max_div); });
 }
 
 int64_t lbm_local_cells(lbm_handle *h) {

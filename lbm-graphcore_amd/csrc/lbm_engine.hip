@@ -928,6 +928,7 @@ void lbm_handle::destroy() {
     prof_release();
     forces_release();
     avg_end();
+    grad_release();
     for (auto &s : subs) {
         if (hipSetDevice(s.dev) != hipSuccess) continue;
         (void)hipDeviceSynchronize();

@@ -8,6 +8,8 @@
 //                         (wall list, kernels and their host side);
 //   lbm_averages.hip      time-averaged fields and Reynolds stresses: fp64
 //                         sums beside the lattice (kernels and their host side);
+//   lbm_gradients.hip     vorticity, divergence, strain rate and Q of the
+//                         current lattice (kernels and their host side);
 //   lbm_exchange.hip      partition rule, torus neighbours, halo destinations,
 //                         the posted exchange (RCCL or device copies);
 //   lbm_split.hip         work decomposition: boundary / interior split,
@@ -97,6 +99,10 @@ struct State;  // wall lists of a handle that asked for wall forces (lbm_forces.
 }
 namespace avg {
 struct State;  // accumulators of a handle that is averaging (lbm_moments.hpp)
+}
+namespace grad {
+struct State;     // edge-velocity buffers of a handle that asked for gradients (lbm_gradients.hip)
+struct GradArgs;  // lbm_gradients.hpp
 }
 }  // namespace lbm
 
@@ -413,5 +419,11 @@ struct lbm_handle {
     void avg_store_sums(double *const *out);
     void avg_store(float *const *out);
     void avg_end();
+    // velocity gradients (lbm_gradients.hip; include/lbm_gradients_hip.h)
+    lbm::grad::State *gradients = nullptr;  // built at the first gradient call
+    std::vector<lbm::grad::GradArgs> grad_prepare();
+    void grad_release();
+    void store_gradients(float *const *out, bool local = false);
+    void gradient_stats(double *sum_w2, double *sum_s2, float *max_w, float *max_div);
     void destroy();
 };

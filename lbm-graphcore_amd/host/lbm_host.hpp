@@ -295,6 +295,58 @@ inline bool writeMeanState(const std::string &filename, const Params &p, const O
     return true;
 }
 
+// ---- velocity gradients (include/lbm_gradients_hip.h) ----
+
+// vorticity, divergence, strain, q (LBM_GRAD_* order), planar float[ny][nx]:
+// the header's fp32 expressions over macroscopic()'s velocities of the AoS
+// cells, periodic central differences, obstacle cells +0.
+inline void velocityGradients(const Params &p, const Obstacles &o, const std::vector<float> &cells,
+                              std::vector<float> (&f)[4]) {
+    const size_t nx = p.nx, ny = p.ny;
+    std::vector<float> U(nx * ny), V(nx * ny);
+    for (size_t y = 0; y < ny; ++y)
+        for (size_t x = 0; x < nx; ++x) {
+            const Macro m = macroscopic(p, o, cells, x, y);
+            U[x + y * nx] = m.ux;
+            V[x + y * nx] = m.uy;
+        }
+    for (auto &a : f) a.assign(nx * ny, 0.f);
+    for (size_t y = 0; y < ny; ++y)
+        for (size_t x = 0; x < nx; ++x) {
+            if (o.at(x, y)) continue;
+            const size_t xe = x + 1 == nx ? 0 : x + 1, xw = x == 0 ? nx - 1 : x - 1;
+            const size_t yn = y + 1 == ny ? 0 : y + 1, ys = y == 0 ? ny - 1 : y - 1;
+            const float gxx = (U[xe + y * nx] - U[xw + y * nx]) * 0.5f, gxy = (U[x + yn * nx] - U[x + ys * nx]) * 0.5f;
+            const float gyx = (V[xe + y * nx] - V[xw + y * nx]) * 0.5f, gyy = (V[x + yn * nx] - V[x + ys * nx]) * 0.5f;
+            const float sxy = (gxy + gyx) * 0.5f;
+            const float s2 = ((gxx * gxx) + (gyy * gyy)) + ((sxy * sxy) * 2.f);
+            const size_t i = x + y * nx;
+            f[0][i] = gyx - gxy;
+            f[1][i] = gxx + gyy;
+            f[2][i] = sqrtf(s2);
+            f[3][i] = (((gxx * gxx) + (gyy * gyy)) * -0.5f) - (gxy * gyx);
+        }
+}
+
+// gradient_state.dat from the four planar float[ny][nx] arrays (LBM_GRAD_*
+// order): `ii jj vorticity divergence strain q obstacle`, through the row
+// formatter of final_state.dat
+inline bool writeGradientState(const std::string &filename, const Params &p, const Obstacles &o,
+                               const std::vector<float> (&f)[4]) {
+    const size_t n = p.nx * p.ny;
+    for (const auto &a : f)
+        if (a.size() != n) return false;
+    std::ofstream file(filename);
+    if (!file.is_open()) return false;
+    for (size_t jj = 0; jj < p.ny; ++jj)
+        for (size_t ii = 0; ii < p.nx; ++ii) {
+            const size_t i = ii + jj * p.nx;
+            const float v[4] = {f[0][i], f[1][i], f[2][i], f[3][i]};
+            writeCellRow(file, ii, jj, v, 4, o.at(ii, jj));
+        }
+    return true;
+}
+
 // forces.dat: `body fx fy links` per body, then `total fx fy links`
 inline bool writeForces(const std::string &filename, const BodyForces &f) {
     FILE *file = fopen(filename.c_str(), "w");

@@ -3,7 +3,7 @@
 //
 //   lbm_runner --params P --obstacles O [-n N] [--device gpu|loopback|cpu] [-d] [--exe ignored]
 //              [--runs 5] [--kernel auto|resident|stream|step2|vec4|scalar|pipeline] [--spl S] [--out-dir DIR]
-//              [--tolerance] [--device-fields] [--forces] [--mean-every N] [--json FILE]
+//              [--tolerance] [--device-fields] [--forces] [--mean-every N] [--gradients] [--json FILE]
 //
 // Flow (same program numbering as the reference):
 //   load params/obstacles -> initialise cells on host -> create engine
@@ -29,6 +29,10 @@
 // run: `x y mean_ux mean_uy mean_pressure c_uxux c_uxuy c_uyuy c_pp obstacle`
 // per cell in final_state.dat's row format; av_vels.dat and final_state.dat
 // are the plain run's.
+// --gradients writes gradient_state.dat after the run: `x y vorticity
+// divergence strain q obstacle` per cell in final_state.dat's row format
+// (lbm_gradients_hip.h) -- from lbm_store_gradients on the GPU, from
+// lbmhost::velocityGradients of the stored cells with --device cpu.
 // --device loopback places all N sub-domains on GPU 0 (the emulator analogue
 // of --device ipumodel: exercises the multi-GPU halo path on one device).
 // --device cpu runs the same fused step on the host's cores (lbm_cpu.hpp:
@@ -49,6 +53,7 @@
 #include "lbm_averages_hip.h"
 #include "lbm_cpu.hpp"
 #include "lbm_forces_hip.h"
+#include "lbm_gradients_hip.h"
 #include "lbm_host.hpp"
 
 namespace {
@@ -76,6 +81,8 @@ void usage(const char *exe) {
               << "      --mean-every arg also write mean_state.dat: time means of u_x, u_y, pressure and their central\n"
               << "                       second moments (Reynolds stresses, pressure variance), sampled on the device\n"
               << "                       every arg steps\n"
+              << "      --gradients      also write gradient_state.dat: vorticity, divergence, strain-rate magnitude and\n"
+              << "                       the Q criterion (Okubo-Weiss) of the final state\n"
               << "      --out-dir arg    directory for av_vels.dat / final_state.dat (default: .)\n"
               << "      --graph-steps arg  replay the step loop as hipGraphs of 2*arg launches (0 = library default, <0 = off)\n"
               << "      --dump-partitioning arg  write the sub-domain decomposition as JSON\n"
@@ -97,7 +104,7 @@ std::string json_str(const std::string &v) {
 
 // --device cpu: the reference's program sequence on the host backend
 int run_cpu(const lbmhost::Params &params, const lbmhost::Obstacles &obstacles, const std::string &outDir, int runs,
-            bool forces) {
+            bool forces, bool gradients) {
     std::cout << "Running on the host CPU (" << lbmcpu::Engine::threads()
               << " threads; bitwise numerics: the reference's LastChance.cpp arithmetic)" << std::endl;
     auto cells = lbmhost::initialiseCells(params);
@@ -118,6 +125,11 @@ int run_cpu(const lbmhost::Params &params, const lbmhost::Obstacles &obstacles, 
             std::vector<int32_t> labels;
             const int32_t nbodies = lbmhost::labelBodies(obstacles, labels);
             lbmhost::writeForces(outDir + "/forces.dat", lbmhost::wallForces(params, obstacles, cells, labels, nbodies));
+        }
+        if (gradients) {
+            std::vector<float> grads[LBM_GRAD_FIELDS];
+            lbmhost::velocityGradients(params, obstacles, cells, grads);
+            lbmhost::writeGradientState(outDir + "/gradient_state.dat", params, obstacles, grads);
         }
     });
     std::cout << "==done==" << std::endl;
@@ -149,7 +161,7 @@ int main(int argc, char *argv[]) {
     std::vector<std::string> gpuOnly;  // GPU-only options given on the command line
     int spl = 0;
     int numGpus = 1, runs = 5, graphSteps = 0, meanEvery = 0;
-    bool debug = false, tolerance = false, deviceFields = false, forces = false;
+    bool debug = false, tolerance = false, deviceFields = false, forces = false, gradients = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         std::string val;
@@ -202,6 +214,8 @@ int main(int argc, char *argv[]) {
             gpuOnly.push_back(a);
         } else if (a == "--forces") {
             forces = true;
+        } else if (a == "--gradients") {
+            gradients = true;
         } else if (a == "--mean-every") {
             if (!next(v)) { usage(argv[0]); return EXIT_FAILURE; }
             meanEvery = std::atoi(v.c_str());
@@ -278,7 +292,7 @@ int main(int argc, char *argv[]) {
             std::cerr << " (the host backend runs the reference arithmetic on one domain)" << std::endl;
             return EXIT_FAILURE;
         }
-        return run_cpu(*params, *obstacles, outDir, runs, forces);
+        return run_cpu(*params, *obstacles, outDir, runs, forces, gradients);
     }
     const int ndev = lbm_device_count();
     if (ndev <= 0) {
@@ -352,6 +366,7 @@ int main(int argc, char *argv[]) {
     float *const avOut = meanEvery > 0 ? nullptr : av_vels.data();
     std::vector<float> f_ux, f_uy, f_u, f_pressure;  // --device-fields: final_state.dat's columns, planar
     lbmhost::BodyForces bodyForces;                   // --forces: forces.dat
+    std::vector<float> grads[LBM_GRAD_FIELDS];        // --gradients: gradient_state.dat's columns, planar
     lbmhost::timedStep("Running copy to host step", [&]() {
         if (deviceFields) {
             const size_t n = params->nx * params->ny;
@@ -373,6 +388,14 @@ int main(int argc, char *argv[]) {
             lbmhost::check(lbm_avg_store(h, out), h, "lbm_avg_store");
             lbmhost::check(lbm_avg_end(h), h, "lbm_avg_end");
         }
+        if (gradients) {
+            float *out[LBM_GRAD_FIELDS];
+            for (int f = 0; f < LBM_GRAD_FIELDS; ++f) {
+                grads[f].assign(params->nx * params->ny, 0.f);
+                out[f] = grads[f].data();
+            }
+            lbmhost::check(lbm_store_gradients(h, out), h, "lbm_store_gradients");
+        }
         if (forces) {
             std::vector<int32_t> labels;
             const int32_t nbodies = lbmhost::labelBodies(*obstacles, labels);
@@ -390,6 +413,7 @@ int main(int argc, char *argv[]) {
     });
     lbmhost::timedStep("Writing output files ", [&]() {
         if (forces) lbmhost::writeForces(outDir + "/forces.dat", bodyForces);
+        if (gradients) lbmhost::writeGradientState(outDir + "/gradient_state.dat", *params, *obstacles, grads);
         if (!means[0].empty()) lbmhost::writeMeanState(outDir + "/mean_state.dat", *params, *obstacles, means);
         lbmhost::writeAverageVelocities(outDir + "/av_vels.dat", av_vels);
         if (deviceFields)

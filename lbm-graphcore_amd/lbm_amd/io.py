@@ -340,6 +340,78 @@ def moment_means(sums, n: int):
     return out
 
 
+# ---- velocity gradients: the definition of include/lbm_gradients_hip.h in numpy ----
+
+def _central(f, axis):
+    """(f[+1] - f[-1]) * 0.5f along `axis`, periodic, in fp32."""
+    return ((np.roll(f, -1, axis) - np.roll(f, 1, axis)) * np.float32(0.5)).astype(np.float32)
+
+
+def velocity_gradients(ux, uy, obstacles):
+    """{"vorticity", "divergence", "strain", "q", "s2"}: float32[ny][nx] each, from the
+    planar velocities fields() gives -- central periodic differences, every operation in
+    fp32 in the order include/lbm_gradients_hip.h writes, obstacle cells +0.  ("s2" = S:S
+    is not a field of the C ABI: gradient_stats sums it.)"""
+    u, v = (np.asarray(f, np.float32) for f in (ux, uy))
+    half, two = np.float32(0.5), np.float32(2)
+    gxx, gxy = _central(u, 1), _central(u, 0)
+    gyx, gyy = _central(v, 1), _central(v, 0)
+    sxy = (gxy + gyx) * half
+    diag = (gxx * gxx) + (gyy * gyy)
+    s2 = diag + ((sxy * sxy) * two)
+    out = {"vorticity": gyx - gxy, "divergence": gxx + gyy, "strain": np.sqrt(s2, dtype=np.float32),
+           "q": (diag * np.float32(-0.5)) - (gxy * gyx), "s2": s2}
+    ob = np.asarray(obstacles).reshape(u.shape).astype(bool)
+    return {k: np.where(ob, np.float32(0), f).astype(np.float32) for k, f in out.items()}
+
+
+def velocity_gradients3d(ux, uy, uz, obstacles):
+    """{"wx", "wy", "wz", "vorticity", "divergence", "strain", "q", "s2"}:
+    float32[nz][ny][nx] each, the D3Q19 definition of include/lbm_gradients_hip.h."""
+    u, v, w = (np.asarray(f, np.float32) for f in (ux, uy, uz))
+    half, two = np.float32(0.5), np.float32(2)
+    gxx, gxy, gxz = _central(u, 2), _central(u, 1), _central(u, 0)
+    gyx, gyy, gyz = _central(v, 2), _central(v, 1), _central(v, 0)
+    gzx, gzy, gzz = _central(w, 2), _central(w, 1), _central(w, 0)
+    wx, wy, wz = gzy - gyz, gxz - gzx, gyx - gxy
+    sxy, sxz, syz = (gxy + gyx) * half, (gxz + gzx) * half, (gyz + gzy) * half
+    diag = ((gxx * gxx) + (gyy * gyy)) + (gzz * gzz)
+    s2 = diag + ((((sxy * sxy) + (sxz * sxz)) + (syz * syz)) * two)
+    out = {"wx": wx, "wy": wy, "wz": wz,
+           "vorticity": np.sqrt(((wx * wx) + (wy * wy)) + (wz * wz), dtype=np.float32),
+           "divergence": (gxx + gyy) + gzz, "strain": np.sqrt(s2, dtype=np.float32),
+           "q": (diag * np.float32(-0.5)) - (((gxy * gyx) + (gxz * gzx)) + (gyz * gzy)), "s2": s2}
+    ob = np.asarray(obstacles).reshape(u.shape).astype(bool)
+    return {k: np.where(ob, np.float32(0), f).astype(np.float32) for k, f in out.items()}
+
+
+def gradient_stats(fields, obstacles):
+    """(sum_w2, sum_s2, max_w, max_div) over the fluid cells of the dict
+    velocity_gradients / velocity_gradients3d returns: the sums of (double)vorticity^2
+    (3-D: ((double)wx*wx + (double)wy*wy) + (double)wz*wz) and of (double)s2 by math.fsum,
+    the maxima of |vorticity| and |divergence| as float32."""
+    import math
+    fluid = ~np.asarray(obstacles).reshape(fields["s2"].shape).astype(bool)
+    d = {k: np.asarray(f, np.float32)[fluid].astype(np.float64) for k, f in fields.items()}
+    if "wx" in d:
+        w2 = (d["wx"] * d["wx"] + d["wy"] * d["wy"]) + d["wz"] * d["wz"]
+    else:
+        w2 = d["vorticity"] * d["vorticity"]
+    if not fluid.any():
+        return 0.0, 0.0, np.float32(0), np.float32(0)
+    return (math.fsum(w2.tolist()), math.fsum(d["s2"].tolist()),
+            np.float32(np.abs(d["vorticity"]).max()), np.float32(np.abs(d["divergence"]).max()))
+
+
+def read_gradient_state(filename: str, nx: int, ny: int):
+    """gradient_state.dat (`x y vorticity divergence strain q obstacle`, y outer) back into
+    {"vorticity", "divergence", "strain", "q"}: float32[ny][nx], and "obstacle": uint8."""
+    t = np.loadtxt(filename, dtype=np.float64).reshape(ny, nx, 7)
+    out = {n: t[..., 2 + i].astype(np.float32) for i, n in enumerate(("vorticity", "divergence", "strain", "q"))}
+    out["obstacle"] = t[..., 6].astype(np.uint8)
+    return out
+
+
 def write_average_velocities(filename: str, av_vels) -> bool:
     """`i:\\t%.12e` per step (iostream scientific, precision 12)."""
     try:

@@ -66,6 +66,16 @@ EXPORTED_AVERAGES = [
 AVG_FIELDS = ("ux", "uy", "pressure", "uxux", "uxuy", "uyuy", "pp")
 AVG_FIELDS3D = ("ux", "uy", "uz", "pressure", "uxux", "uxuy", "uxuz", "uyuy", "uyuz", "uzuz", "pp")
 AVG_MEAN, AVG_SECOND = 1, 2
+# every symbol include/lbm_gradients_hip.h declares (vorticity, divergence, strain rate, Q; both engines)
+EXPORTED_GRADIENTS = [
+    "lbm_store_gradients", "lbm_store_gradients_local", "lbm_gradient_stats",
+    "lbm3d_store_gradients", "lbm3d_store_gradients_box", "lbm3d_gradient_stats",
+]
+# index order of the output-pointer arrays (LBM_GRAD_* / LBM3D_GRAD_*)
+GRAD_FIELDS = ("vorticity", "divergence", "strain", "q")
+GRAD_FIELDS3D = ("wx", "wy", "wz", "vorticity", "divergence", "strain", "q")
+# work shape of the D2Q9 gradient kernel (csrc/lbm_gradients.hpp): columns a wave owns, rows of a segment
+GRAD_STRIP_COLS, GRAD_SEGMENT_ROWS = 248, 32
 Q3 = 19
 
 
@@ -228,6 +238,12 @@ def load_library() -> ctypes.CDLL:
         "lbm3d_avg_store_sums": ([H, ctypes.POINTER(f64p)], ctypes.c_int),
         "lbm3d_avg_store": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
         "lbm3d_avg_end": ([H], ctypes.c_int),
+        "lbm_store_gradients": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
+        "lbm_store_gradients_local": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
+        "lbm_gradient_stats": ([H, f64p, f64p, f32p, f32p], ctypes.c_int),
+        "lbm3d_store_gradients": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
+        "lbm3d_store_gradients_box": ([H, ctypes.POINTER(Box3D), ctypes.POINTER(f32p)], ctypes.c_int),
+        "lbm3d_gradient_stats": ([H, f64p, f64p, f32p, f32p], ctypes.c_int),
         "lbm3d_total_free_cells": ([H], i64),
         "lbm3d_local_slabs": ([H, i32p, i32p, i32, i32p], ctypes.c_int),
         "lbm3d_last_error": ([H], ctypes.c_char_p),
@@ -427,11 +443,83 @@ class _Averages:
         return self._avg_store(self._avg_fn("store"), which, np.float32, ctypes.c_float)
 
 
-class Engine(_WallForces, _Averages):
+class _Gradients:
+    """Engine / Engine3D methods over include/lbm_gradients_hip.h; the class sets
+    _FORCE_PREFIX ("lbm_" / "lbm3d_"), _force_shape() and _GRAD_FIELDS."""
+
+    def _grad_which(self, which):
+        names = self._GRAD_FIELDS
+        which = names if which is None else tuple(which)
+        bad = [n for n in which if n not in names]
+        if bad or len(set(which)) != len(which):
+            raise ValueError(f"gradient fields are a subset of {names}, each at most once; got {which}")
+        return which
+
+    def _grad_ptrs(self, out):
+        ptrs = (ctypes.POINTER(ctypes.c_float) * len(self._GRAD_FIELDS))()
+        for i, n in enumerate(self._GRAD_FIELDS):
+            if n in out:
+                ptrs[i] = _f32(out[n])
+        return ptrs
+
+    def gradients(self, which=None):
+        """{name: float32 array} of the requested fields ("vorticity", "divergence",
+        "strain", "q"; D3Q19 also "wx", "wy", "wz"), derived on the device from the
+        current lattice (lbm_store_gradients): lio.velocity_gradients[3d] of fields(), bit
+        for bit.  Default: every field."""
+        which = self._grad_which(which)
+        out = {n: np.zeros(self._force_shape(), np.float32) for n in which}
+        self._check(getattr(self._L, self._FORCE_PREFIX + "store_gradients")(self._h, self._grad_ptrs(out)))
+        return out
+
+    def gradient_stats(self):
+        """(sum_w2, sum_s2, max_w, max_div) over this handle's fluid cells
+        (lbm_gradient_stats): the fp64 sums of vorticity^2 and S:S and the largest
+        |vorticity| and |divergence|.  Enstrophy = sum_w2 / 2; dissipation = 2 nu sum_s2."""
+        w2, s2 = ctypes.c_double(), ctypes.c_double()
+        mw, md = ctypes.c_float(), ctypes.c_float()
+        self._check(getattr(self._L, self._FORCE_PREFIX + "gradient_stats")(
+            self._h, ctypes.byref(w2), ctypes.byref(s2), ctypes.byref(mw), ctypes.byref(md)))
+        return w2.value, s2.value, mw.value, md.value
+
+
+class Engine(_WallForces, _Averages, _Gradients):
     """One lbm_handle: the HIP counterpart of the reference's poplar::Engine."""
 
     _FORCE_PREFIX = "lbm_"
     _AVG_FIELDS = AVG_FIELDS
+    _GRAD_FIELDS = GRAD_FIELDS
+
+    def gradients_local(self, which=None):
+        """[{name: float32[h][w]}] per local rect (local_rects() order; lbm_store_gradients_local)."""
+        which = self._grad_which(which)
+        rects = self.local_rects()
+        n = int(self._L.lbm_local_cells(self._h))
+        packed = {f: np.zeros(n, np.float32) for f in which}
+        self._check(self._L.lbm_store_gradients_local(self._h, self._grad_ptrs(packed)))
+        out, off = [], 0
+        for (_, _, w, h) in rects:
+            out.append({f: packed[f][off:off + w * h].reshape(h, w) for f in which})
+            off += w * h
+        return out
+
+    def gradient_history(self, steps: int, every: int, accelerate_first: bool = False):
+        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and sample
+        gradient_stats() after each chunk.  Returns (samples, av_vels): samples is a list of
+        (step, sum_w2, sum_s2, max_w, max_div) with step = steps done so far, av_vels the
+        float32[steps] concatenation of the chunks' average velocities.  Chunking behaves
+        as in force_history."""
+        steps, every = int(steps), int(every)
+        if steps < 0 or every < 1:
+            raise ValueError("steps >= 0 and every >= 1")
+        samples, av, done = [], [], 0
+        while done < steps:
+            n = min(every, steps - done)
+            self.run_steps(n, accelerate_first and done == 0)
+            av.append(self.store(cells=False, n_av=n)[1].copy())
+            done += n
+            samples.append((done,) + self.gradient_stats())
+        return samples, (np.concatenate(av) if av else np.zeros(0, np.float32))
 
     def run_averaged(self, steps: int, every: int, accelerate_first: bool = False):
         """Advance `steps` steps in run_steps(every) chunks (the remainder last) and
@@ -679,11 +767,36 @@ class Engine(_WallForces, _Averages):
             pass
 
 
-class Engine3D(_WallForces, _Averages):
+class Engine3D(_WallForces, _Averages, _Gradients):
     """One lbm3d_handle: the D3Q19 extension engine (include/lbm3d_hip.h)."""
 
     _FORCE_PREFIX = "lbm3d_"
     _AVG_FIELDS = AVG_FIELDS3D
+    _GRAD_FIELDS = GRAD_FIELDS3D
+
+    def gradients_box(self, x0: int, y0: int, z0: int, nx: int, ny: int, nz: int, which=None):
+        """{name: float32[nz][ny][nx]} of the cells [x0, x0+nx) x [y0, y0+ny) x [z0, z0+nz)
+        (lbm3d_store_gradients_box).  The stencils of the box's outer cells still read
+        their periodic neighbours; a box that is empty or leaves the domain raises LbmError."""
+        which = self._grad_which(which)
+        box = Box3D(int(x0), int(y0), int(z0), int(nx), int(ny), int(nz))
+        out = {n: np.zeros((max(box.nz, 0), max(box.ny, 0), max(box.nx, 0)), np.float32) for n in which}
+        self._check(self._L.lbm3d_store_gradients_box(self._h, ctypes.byref(box), self._grad_ptrs(out)))
+        return out
+
+    def gradient_history(self, steps: int, every: int):
+        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and sample
+        gradient_stats() after each chunk: a list of (step, sum_w2, sum_s2, max_w, max_div)."""
+        steps, every = int(steps), int(every)
+        if steps < 0 or every < 1:
+            raise ValueError("steps >= 0 and every >= 1")
+        samples, done = [], 0
+        while done < steps:
+            n = min(every, steps - done)
+            self.run_steps(n)
+            done += n
+            samples.append((done,) + self.gradient_stats())
+        return samples
 
     def run_averaged(self, steps: int, every: int) -> None:
         """Advance `steps` steps in run_steps(every) chunks (the remainder last) and
