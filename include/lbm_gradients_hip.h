@@ -30,8 +30,10 @@
  * An obstacle cell reports +0 in every output.  A fluid cell next to a wall
  * uses the wall cell's 0 velocity at the cell centre: what a post-processor
  * would do with final_state.dat, and first order at a halfway bounce-back wall
- * (second-order wall-corrected differences are not built).  With nx == 1 or
- * ny == 1 the two neighbours coincide and the differences are +0.
+ * (second-order wall-corrected differences are not built; lbm_stress_hip.h
+ * gives a strain rate that is second order there, from the cell's own
+ * non-equilibrium moments).  With nx == 1 or ny == 1 the two neighbours
+ * coincide and the differences are +0.
  *
  * Definition, D3Q19.  The same with nine components
  * g_ab = (u_a[+b] - u_a[-b]) * 0.5f, periodic in x, y and z, from

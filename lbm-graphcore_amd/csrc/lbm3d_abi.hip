@@ -1,12 +1,13 @@
 // lbm3d_abi.hip -- the extern "C" functions of include/lbm3d_hip.h,
 // include/lbm3d_fields_hip.h and the D3Q19 functions of
 // include/lbm_forces_hip.h, include/lbm_averages_hip.h and
-// include/lbm_gradients_hip.h over the engine
+// include/lbm_gradients_hip.h and include/lbm_stress_hip.h over the engine
 // (lbm3d_engine.hpp), and the posting order of its RCCL ghost exchange.
 
 #include "lbm3d_engine.hpp"
 #include "lbm_averages_hip.h"
 #include "lbm_gradients_hip.h"
+#include "lbm_stress_hip.h"
 
 namespace lbm {
 std::array<lbm_xfer, 4> slab_posts(int rank, int world, long long floats) {
@@ -145,6 +146,23 @@ int lbm3d_store_gradients_box(lbm3d_handle *h, const lbm3d_box *box, float *cons
 int lbm3d_gradient_stats(lbm3d_handle *h, double *sum_w2, double *sum_s2, float *max_w, float *max_div) {
     if (!h) return LBM_E_INVALID;
     return guarded(h, [&] { h->gradient_stats(sum_w2, sum_s2, max_w, max_div); });
+}
+
+int lbm3d_store_stress(lbm3d_handle *h, float *const out[LBM3D_STRESS_FIELDS]) {
+    if (!h) return LBM_E_INVALID;
+    const lbm3d_box all{0, 0, 0, h->p.nx, h->p.ny, h->p.nz};
+    return lbm3d_store_stress_box(h, &all, out);
+}
+
+int lbm3d_store_stress_box(lbm3d_handle *h, const lbm3d_box *box, float *const out[LBM3D_STRESS_FIELDS]) {
+    if (!h || !box) return LBM_E_INVALID;
+    return guarded(h, [&] { h->store_stress_box(*box, out); });
+}
+
+int lbm3d_stress_stats(lbm3d_handle *h, double *sum_s2, float *max_strain, int64_t *wall_cells,
+                       double *sum_wall_strain, float *max_wall_strain) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->stress_stats(sum_s2, max_strain, wall_cells, sum_wall_strain, max_wall_strain); });
 }
 
 int lbm3d_last_run_seconds(lbm3d_handle *h, double *seconds) {

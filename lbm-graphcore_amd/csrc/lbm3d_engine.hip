@@ -692,6 +692,7 @@ void lbm3d_handle::destroy() {
     walls_release();
     avg_end();
     grad_release();
+    stress_release();
     for (auto &s : slabs) {
         if (hipSetDevice(s.dev) != hipSuccess) continue;
         (void)hipDeviceSynchronize();

@@ -8,6 +8,7 @@
 //   lbm3d_forces.hip   momentum-exchange wall forces (kernels + host side);
 //   lbm3d_averages.hip time-averaged fields and Reynolds stresses (kernels + host side);
 //   lbm3d_gradients.hip vorticity, divergence, strain rate and Q (kernel + host side);
+//   lbm3d_stress.hip   strain rate and wall shear from the non-equilibrium moments (kernel + host side);
 //   lbm3d_abi.hip      the extern "C" functions and the RCCL posting order.
 #pragma once
 
@@ -32,6 +33,10 @@ struct State;  // accumulators of a handle that is averaging (lbm_moments.hpp)
 }
 namespace grad {
 struct Grad3Args;  // lbm_gradients.hpp
+}
+namespace stress {
+struct State3;       // near-wall class maps of a handle that asked for strain statistics (lbm3d_stress.hip)
+struct Stress3Args;  // lbm_stress.hpp
 }
 
 constexpr int Q3 = 19;
@@ -244,4 +249,12 @@ struct lbm3d_handle {
     lbm::grad::Grad3Args grad_args(size_t k, int hp, int x0, int y0, int z0, int bx, int by, int bz) const;
     void store_gradients_box(const lbm3d_box &b, float *const *host);
     void gradient_stats(double *sum_w2, double *sum_s2, float *max_w, float *max_div);
+    // lbm3d_stress.hip (include/lbm_stress_hip.h)
+    lbm::stress::State3 *stress = nullptr;  // built at the first statistics call
+    lbm::stress::Stress3Args stress_args(const lbm::Slab &s, int x0, int y0, int z0, int bx, int by, int bz) const;
+    void stress_build();
+    void stress_release();
+    void store_stress_box(const lbm3d_box &b, float *const *host);
+    void stress_stats(double *sum_s2, float *max_strain, int64_t *wall_cells, double *sum_wall_strain,
+                      float *max_wall_strain);
 };

@@ -1,11 +1,12 @@
 // lbm_abi.hip -- the extern "C" functions of include/lbm_hip.h and the D2Q9
 // functions of include/lbm_forces_hip.h, include/lbm_averages_hip.h and
-// include/lbm_gradients_hip.h over the engine.
+// include/lbm_gradients_hip.h and include/lbm_stress_hip.h over the engine.
 
 #include "lbm_averages_hip.h"
 #include "lbm_engine.hpp"
 #include "lbm_forces_hip.h"
 #include "lbm_gradients_hip.h"
+#include "lbm_stress_hip.h"
 
 // --------------------------------------------------------------------------
 // C ABI
@@ -230,6 +231,22 @@ int lbm_store_gradients_local(lbm_handle *h, float *const out[LBM_GRAD_FIELDS]) 
 int lbm_gradient_stats(lbm_handle *h, double *sum_w2, double *sum_s2, float *max_w, float *max_div) {
     if (!h) return LBM_E_INVALID;
     return guarded(h, [&] { h->gradient_stats(sum_w2, sum_s2, max_w, max_div); });
+}
+
+int lbm_store_stress(lbm_handle *h, float *const out[LBM_STRESS_FIELDS]) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->store_stress(out); });
+}
+
+int lbm_store_stress_local(lbm_handle *h, float *const out[LBM_STRESS_FIELDS]) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->store_stress(out, true); });
+}
+
+int lbm_stress_stats(lbm_handle *h, double *sum_s2, float *max_strain, int64_t *wall_cells, double *sum_wall_strain,
+                     float *max_wall_strain) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->stress_stats(sum_s2, max_strain, wall_cells, sum_wall_strain, max_wall_strain); });
 }
 
 int64_t lbm_local_cells(lbm_handle *h) {

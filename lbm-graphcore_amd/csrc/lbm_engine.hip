@@ -929,6 +929,7 @@ void lbm_handle::destroy() {
     forces_release();
     avg_end();
     grad_release();
+    stress_release();
     for (auto &s : subs) {
         if (hipSetDevice(s.dev) != hipSuccess) continue;
         (void)hipDeviceSynchronize();

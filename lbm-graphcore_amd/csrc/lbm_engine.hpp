@@ -10,6 +10,8 @@
 //                         sums beside the lattice (kernels and their host side);
 //   lbm_gradients.hip     vorticity, divergence, strain rate and Q of the
 //                         current lattice (kernels and their host side);
+//   lbm_stress.hip        strain rate and wall shear from the non-equilibrium
+//                         moments of the current lattice (kernel and its host side);
 //   lbm_exchange.hip      partition rule, torus neighbours, halo destinations,
 //                         the posted exchange (RCCL or device copies);
 //   lbm_split.hip         work decomposition: boundary / interior split,
@@ -103,6 +105,10 @@ struct State;  // accumulators of a handle that is averaging (lbm_moments.hpp)
 namespace grad {
 struct State;     // edge-velocity buffers of a handle that asked for gradients (lbm_gradients.hip)
 struct GradArgs;  // lbm_gradients.hpp
+}
+namespace stress {
+struct State;       // near-wall class maps of a handle that asked for strain statistics (lbm_stress.hip)
+struct StressArgs;  // lbm_stress.hpp
 }
 }  // namespace lbm
 
@@ -425,5 +431,13 @@ struct lbm_handle {
     void grad_release();
     void store_gradients(float *const *out, bool local = false);
     void gradient_stats(double *sum_w2, double *sum_s2, float *max_w, float *max_div);
+    // non-equilibrium strain rate (lbm_stress.hip; include/lbm_stress_hip.h)
+    lbm::stress::State *stress = nullptr;  // built at the first statistics call
+    lbm::stress::StressArgs stress_args(const Sub &s) const;
+    void stress_build();
+    void stress_release();
+    void store_stress(float *const *out, bool local = false);
+    void stress_stats(double *sum_s2, float *max_strain, int64_t *wall_cells, double *sum_wall_strain,
+                      float *max_wall_strain);
     void destroy();
 };

@@ -16,6 +16,10 @@
 //                           the momentum-exchange wall forces of
 //                           include/lbm_forces_hip.h on the host (lbm_runner
 //                           --forces; no reference counterpart)
+//   nearWall, neqStrain, writeStressState
+//                           the non-equilibrium strain rate of
+//                           include/lbm_stress_hip.h on the host (lbm_runner
+//                           --stress; no reference counterpart)
 //   timedStep               main/include/GraphcoreUtils.hpp:130-138
 #pragma once
 
@@ -343,6 +347,77 @@ inline bool writeGradientState(const std::string &filename, const Params &p, con
             const size_t i = ii + jj * p.nx;
             const float v[4] = {f[0][i], f[1][i], f[2][i], f[3][i]};
             writeCellRow(file, ii, jj, v, 4, o.at(ii, jj));
+        }
+    return true;
+}
+
+// ---- non-equilibrium strain rate (include/lbm_stress_hip.h) ----
+
+// near[ny][nx] = 1 on the fluid cells with a blocked neighbour among the eight (periodic)
+inline std::vector<uint8_t> nearWall(const Obstacles &o) {
+    std::vector<uint8_t> near(o.nx * o.ny, 0);
+    for (size_t y = 0; y < o.ny; ++y)
+        for (size_t x = 0; x < o.nx; ++x) {
+            if (o.at(x, y)) continue;
+            for (int dy = -1; dy <= 1; ++dy)
+                for (int dx = -1; dx <= 1; ++dx)
+                    if ((dx || dy) && o.at((x + o.nx + dx) % o.nx, (y + o.ny + dy) % o.ny)) near[x + y * o.nx] = 1;
+        }
+    return near;
+}
+
+// sxx, sxy, syy, strain (LBM_STRESS_* order), planar float[ny][nx], from the
+// non-equilibrium second moment of the stored AoS cells: the header's fp32
+// expressions, obstacle cells +0.  false for omega = 1.
+inline bool neqStrain(const Params &p, const Obstacles &o, const std::vector<float> &cells,
+                      std::vector<float> (&f)[4]) {
+    const size_t nx = p.nx, ny = p.ny;
+    const float omo = 1.f - p.omega;
+    if (omo == 0.f) return false;
+    const float coef = (-1.5f * p.omega) / omo;
+    for (auto &a : f) a.assign(nx * ny, 0.f);
+    for (size_t y = 0; y < ny; ++y)
+        for (size_t x = 0; x < nx; ++x) {
+            if (o.at(x, y)) continue;
+            const size_t i = x + y * nx;
+            const float *c = &cells[i * NumSpeeds];
+            const Macro m = macroscopic(p, o, cells, x, y);
+            float rho = 0.f;
+            for (unsigned k = 0; k < NumSpeeds; ++k) rho += c[k];
+            const float pxx = ((((c[1] + c[3]) + c[5]) + c[6]) + c[7]) + c[8];
+            const float pyy = ((((c[2] + c[4]) + c[5]) + c[6]) + c[7]) + c[8];
+            const float pxy = (c[5] + c[7]) - (c[6] + c[8]);
+            const float pr = rho * (1.f / 3.f);
+            const float nxx = (pxx - pr) - ((rho * m.ux) * m.ux);
+            const float nyy = (pyy - pr) - ((rho * m.uy) * m.uy);
+            const float nxy = pxy - ((rho * m.ux) * m.uy);
+            const float k = coef / rho;
+            const float sxx = nxx * k, syy = nyy * k, sxy = nxy * k;
+            f[0][i] = sxx;
+            f[1][i] = sxy;
+            f[2][i] = syy;
+            f[3][i] = sqrtf(((sxx * sxx) + (syy * syy)) + ((sxy * sxy) * 2.f));
+        }
+    return true;
+}
+
+// stress_state.dat from the four planar float[ny][nx] arrays (LBM_STRESS_*
+// order) and the near-wall map: `ii jj sxx sxy syy strain near_wall obstacle`,
+// the values through the row formatter of final_state.dat
+inline bool writeStressState(const std::string &filename, const Params &p, const Obstacles &o,
+                             const std::vector<float> (&f)[4], const std::vector<uint8_t> &near) {
+    const size_t n = p.nx * p.ny;
+    for (const auto &a : f)
+        if (a.size() != n) return false;
+    if (near.size() != n) return false;
+    std::ofstream file(filename);
+    if (!file.is_open()) return false;
+    for (size_t jj = 0; jj < p.ny; ++jj)
+        for (size_t ii = 0; ii < p.nx; ++ii) {
+            const size_t i = ii + jj * p.nx;
+            file << ii << " " << jj << std::setprecision(12) << std::scientific;
+            for (int k = 0; k < 4; ++k) file << " " << f[k][i];
+            file << " " << (int)near[i] << " " << (int)o.at(ii, jj) << "\n";
         }
     return true;
 }

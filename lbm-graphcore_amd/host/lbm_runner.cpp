@@ -3,7 +3,8 @@
 //
 //   lbm_runner --params P --obstacles O [-n N] [--device gpu|loopback|cpu] [-d] [--exe ignored]
 //              [--runs 5] [--kernel auto|resident|stream|step2|vec4|scalar|pipeline] [--spl S] [--out-dir DIR]
-//              [--tolerance] [--device-fields] [--forces] [--mean-every N] [--gradients] [--json FILE]
+//              [--tolerance] [--device-fields] [--forces] [--mean-every N] [--gradients] [--stress]
+//              [--json FILE]
 //
 // Flow (same program numbering as the reference):
 //   load params/obstacles -> initialise cells on host -> create engine
@@ -33,6 +34,10 @@
 // divergence strain q obstacle` per cell in final_state.dat's row format
 // (lbm_gradients_hip.h) -- from lbm_store_gradients on the GPU, from
 // lbmhost::velocityGradients of the stored cells with --device cpu.
+// --stress writes stress_state.dat after the run: `x y sxx sxy syy strain
+// near_wall obstacle` per cell, the values in final_state.dat's format
+// (lbm_stress_hip.h) -- from lbm_store_stress on the GPU, from
+// lbmhost::neqStrain of the stored cells with --device cpu.
 // --device loopback places all N sub-domains on GPU 0 (the emulator analogue
 // of --device ipumodel: exercises the multi-GPU halo path on one device).
 // --device cpu runs the same fused step on the host's cores (lbm_cpu.hpp:
@@ -55,6 +60,7 @@
 #include "lbm_forces_hip.h"
 #include "lbm_gradients_hip.h"
 #include "lbm_host.hpp"
+#include "lbm_stress_hip.h"
 
 namespace {
 
@@ -83,6 +89,8 @@ void usage(const char *exe) {
               << "                       every arg steps\n"
               << "      --gradients      also write gradient_state.dat: vorticity, divergence, strain-rate magnitude and\n"
               << "                       the Q criterion (Okubo-Weiss) of the final state\n"
+              << "      --stress         also write stress_state.dat: the strain-rate tensor and its magnitude from the\n"
+              << "                       non-equilibrium moments of the final state, and the near-wall cells\n"
               << "      --out-dir arg    directory for av_vels.dat / final_state.dat (default: .)\n"
               << "      --graph-steps arg  replay the step loop as hipGraphs of 2*arg launches (0 = library default, <0 = off)\n"
               << "      --dump-partitioning arg  write the sub-domain decomposition as JSON\n"
@@ -104,7 +112,7 @@ std::string json_str(const std::string &v) {
 
 // --device cpu: the reference's program sequence on the host backend
 int run_cpu(const lbmhost::Params &params, const lbmhost::Obstacles &obstacles, const std::string &outDir, int runs,
-            bool forces, bool gradients) {
+            bool forces, bool gradients, bool stress) {
     std::cout << "Running on the host CPU (" << lbmcpu::Engine::threads()
               << " threads; bitwise numerics: the reference's LastChance.cpp arithmetic)" << std::endl;
     auto cells = lbmhost::initialiseCells(params);
@@ -130,6 +138,15 @@ int run_cpu(const lbmhost::Params &params, const lbmhost::Obstacles &obstacles, 
             std::vector<float> grads[LBM_GRAD_FIELDS];
             lbmhost::velocityGradients(params, obstacles, cells, grads);
             lbmhost::writeGradientState(outDir + "/gradient_state.dat", params, obstacles, grads);
+        }
+        if (stress) {
+            std::vector<float> strain[LBM_STRESS_FIELDS];
+            if (!lbmhost::neqStrain(params, obstacles, cells, strain)) {
+                std::cerr << "--stress: omega = 1 leaves no non-equilibrium part in the stored lattice" << std::endl;
+                std::exit(EXIT_FAILURE);
+            }
+            lbmhost::writeStressState(outDir + "/stress_state.dat", params, obstacles, strain,
+                                      lbmhost::nearWall(obstacles));
         }
     });
     std::cout << "==done==" << std::endl;
@@ -161,7 +178,7 @@ int main(int argc, char *argv[]) {
     std::vector<std::string> gpuOnly;  // GPU-only options given on the command line
     int spl = 0;
     int numGpus = 1, runs = 5, graphSteps = 0, meanEvery = 0;
-    bool debug = false, tolerance = false, deviceFields = false, forces = false, gradients = false;
+    bool debug = false, tolerance = false, deviceFields = false, forces = false, gradients = false, stress = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         std::string val;
@@ -216,6 +233,8 @@ int main(int argc, char *argv[]) {
             forces = true;
         } else if (a == "--gradients") {
             gradients = true;
+        } else if (a == "--stress") {
+            stress = true;
         } else if (a == "--mean-every") {
             if (!next(v)) { usage(argv[0]); return EXIT_FAILURE; }
             meanEvery = std::atoi(v.c_str());
@@ -292,7 +311,7 @@ int main(int argc, char *argv[]) {
             std::cerr << " (the host backend runs the reference arithmetic on one domain)" << std::endl;
             return EXIT_FAILURE;
         }
-        return run_cpu(*params, *obstacles, outDir, runs, forces, gradients);
+        return run_cpu(*params, *obstacles, outDir, runs, forces, gradients, stress);
     }
     const int ndev = lbm_device_count();
     if (ndev <= 0) {
@@ -367,6 +386,7 @@ int main(int argc, char *argv[]) {
     std::vector<float> f_ux, f_uy, f_u, f_pressure;  // --device-fields: final_state.dat's columns, planar
     lbmhost::BodyForces bodyForces;                   // --forces: forces.dat
     std::vector<float> grads[LBM_GRAD_FIELDS];        // --gradients: gradient_state.dat's columns, planar
+    std::vector<float> strain[LBM_STRESS_FIELDS];     // --stress: stress_state.dat's columns, planar
     lbmhost::timedStep("Running copy to host step", [&]() {
         if (deviceFields) {
             const size_t n = params->nx * params->ny;
@@ -396,6 +416,14 @@ int main(int argc, char *argv[]) {
             }
             lbmhost::check(lbm_store_gradients(h, out), h, "lbm_store_gradients");
         }
+        if (stress) {
+            float *out[LBM_STRESS_FIELDS];
+            for (int f = 0; f < LBM_STRESS_FIELDS; ++f) {
+                strain[f].assign((size_t)params->nx * params->ny, 0.f);
+                out[f] = strain[f].data();
+            }
+            lbmhost::check(lbm_store_stress(h, out), h, "lbm_store_stress");
+        }
         if (forces) {
             std::vector<int32_t> labels;
             const int32_t nbodies = lbmhost::labelBodies(*obstacles, labels);
@@ -414,6 +442,9 @@ int main(int argc, char *argv[]) {
     lbmhost::timedStep("Writing output files ", [&]() {
         if (forces) lbmhost::writeForces(outDir + "/forces.dat", bodyForces);
         if (gradients) lbmhost::writeGradientState(outDir + "/gradient_state.dat", *params, *obstacles, grads);
+        if (stress)
+            lbmhost::writeStressState(outDir + "/stress_state.dat", *params, *obstacles, strain,
+                                      lbmhost::nearWall(*obstacles));
         if (!means[0].empty()) lbmhost::writeMeanState(outDir + "/mean_state.dat", *params, *obstacles, means);
         lbmhost::writeAverageVelocities(outDir + "/av_vels.dat", av_vels);
         if (deviceFields)

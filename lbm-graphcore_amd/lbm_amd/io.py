@@ -13,6 +13,9 @@
 * wall_links, wall_force_cells, wall_force (+ ...3d), label_bodies
                         -- the momentum-exchange wall forces of include/lbm_forces_hip.h
                            in fp32 numpy (Engine.wall_force(), .wall_force_field(), .body_forces())
+* neq_strain, neq_strain3d, near_wall, near_wall3d, strain_stats
+                        -- the non-equilibrium strain rate of include/lbm_stress_hip.h in fp32
+                           numpy (Engine.strain_rate(), .strain_stats())
 
 Error behaviour follows the reference: loaders return None (std::nullopt)
 and print the reference's message on stderr.  One deliberate strengthening:
@@ -409,6 +412,121 @@ def read_gradient_state(filename: str, nx: int, ny: int):
     t = np.loadtxt(filename, dtype=np.float64).reshape(ny, nx, 7)
     out = {n: t[..., 2 + i].astype(np.float32) for i, n in enumerate(("vorticity", "divergence", "strain", "q"))}
     out["obstacle"] = t[..., 6].astype(np.uint8)
+    return out
+
+
+# ---- non-equilibrium strain rate: the definition of include/lbm_stress_hip.h in numpy ----
+
+def _neq_coef(omega):
+    omega = np.float32(omega)
+    omo = np.float32(1) - omega
+    if omo == 0:
+        raise ValueError("omega = 1: the post-collision lattice carries no non-equilibrium part")
+    return (np.float32(-1.5) * omega) / omo
+
+
+def _neq_finish(n, rho, coef, ob):
+    """s_ab = n_ab * (coef / rho), "s2", "strain"; obstacle cells +0.  `n` maps a component
+    name to n_ab, diagonal components first (names with two equal letters)."""
+    k = coef / rho
+    s = {name: v * k for name, v in n.items()}
+    diag = [s[a] * s[a] for a in s if a[1] == a[2]]
+    off = [s[a] * s[a] for a in s if a[1] != a[2]]
+    d, o = diag[0], off[0]
+    for t in diag[1:]:
+        d = d + t
+    for t in off[1:]:
+        o = o + t
+    s["s2"] = d + (o * np.float32(2))
+    s["strain"] = np.sqrt(s["s2"], dtype=np.float32)
+    return {name: np.where(ob, np.float32(0), f).astype(np.float32) for name, f in s.items()}
+
+
+def neq_strain(cells, obstacles, omega):
+    """{"sxx", "sxy", "syy", "strain", "s2"}: float32[ny][nx] each, the strain rate from
+    the non-equilibrium second moment of the stored (post-collision) AoS cells
+    float32[ny][nx][9] -- every operation in fp32 in the order include/lbm_stress_hip.h
+    writes, obstacle cells +0.  ("s2" = S:S is not a field of the C ABI: strain_stats sums it.)"""
+    c = np.asarray(cells, np.float32)
+    ob = np.asarray(obstacles).reshape(c.shape[:-1]).astype(bool)
+    coef = _neq_coef(omega)
+    t = [c[..., k] for k in range(Q)]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        rho = _seq(t, *range(Q))
+        ux = (_seq(t, 1, 5, 8) - _seq(t, 3, 6, 7)) / rho
+        uy = (_seq(t, 2, 5, 6) - _seq(t, 4, 7, 8)) / rho
+        p = rho * C_SQ
+        n = {"sxx": (_seq(t, 1, 3, 5, 6, 7, 8) - p) - ((rho * ux) * ux),
+             "syy": (_seq(t, 2, 4, 5, 6, 7, 8) - p) - ((rho * uy) * uy),
+             "sxy": ((t[5] + t[7]) - (t[6] + t[8])) - ((rho * ux) * uy)}
+        return _neq_finish(n, rho, coef, ob)
+
+
+def neq_strain3d(cells, obstacles, omega):
+    """{"sxx", "syy", "szz", "sxy", "sxz", "syz", "strain", "s2"}: float32[nz][ny][nx] each,
+    the D3Q19 definition of include/lbm_stress_hip.h from the AoS cells float32[nz][ny][nx][19]."""
+    c = np.asarray(cells, np.float32)
+    ob = np.asarray(obstacles).reshape(c.shape[:-1]).astype(bool)
+    coef = _neq_coef(omega)
+    t = [c[..., k] for k in range(19)]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        rho = _seq(t, *range(19))
+        ux = (_seq(t, 1, 5, 7, 10, 16) - _seq(t, 2, 6, 8, 11, 15)) / rho
+        uy = (_seq(t, 3, 5, 8, 12, 18) - _seq(t, 4, 6, 7, 13, 17)) / rho
+        uz = (_seq(t, 9, 10, 11, 12, 13) - _seq(t, 14, 15, 16, 17, 18)) / rho
+        p = rho * C_SQ
+        n = {"sxx": (_seq(t, 1, 2, 5, 6, 7, 8, 10, 11, 15, 16) - p) - ((rho * ux) * ux),
+             "syy": (_seq(t, 3, 4, 5, 6, 7, 8, 12, 13, 17, 18) - p) - ((rho * uy) * uy),
+             "szz": (_seq(t, *range(9, 19)) - p) - ((rho * uz) * uz),
+             "sxy": ((t[5] + t[6]) - (t[7] + t[8])) - ((rho * ux) * uy),
+             "sxz": ((t[10] + t[15]) - (t[11] + t[16])) - ((rho * ux) * uz),
+             "syz": ((t[12] + t[17]) - (t[13] + t[18])) - ((rho * uy) * uz)}
+        return _neq_finish(n, rho, coef, ob)
+
+
+def _near_wall(obstacles, vectors):
+    ob = np.asarray(obstacles) != 0
+    axes = tuple(range(ob.ndim))
+    near = np.zeros(ob.shape, bool)
+    for e in vectors[1:]:
+        near |= np.roll(ob, tuple(-c for c in reversed(e)), axes)   # rolled[x] = ob[x + e], periodic
+    return near & ~ob
+
+
+def near_wall(obstacles) -> np.ndarray:
+    """bool[ny][nx]: the fluid cells with at least one blocked neighbour among the 8 of the
+    D2Q9 lattice, periodic over the full domain (include/lbm_stress_hip.h)."""
+    return _near_wall(np.asarray(obstacles).reshape(np.shape(obstacles)[-2:]), E2)
+
+
+def near_wall3d(obstacles) -> np.ndarray:
+    """bool[nz][ny][nx]: the same over the 18 neighbours of the D3Q19 lattice."""
+    return _near_wall(obstacles, E3)
+
+
+def strain_stats(fields, obstacles, near):
+    """(sum_s2, max_strain, wall_cells, sum_wall_strain, max_wall_strain) of the dict
+    neq_strain / neq_strain3d returns: over the fluid cells the sum of (double)s2 by
+    math.fsum and the largest strain, over the near-wall cells `near` their number, the
+    sum of (double)strain by math.fsum and the largest strain (float32; 0 over no cell)."""
+    import math
+    shape = fields["s2"].shape
+    fluid = ~np.asarray(obstacles).reshape(shape).astype(bool)
+    near = np.asarray(near).reshape(shape).astype(bool) & fluid
+    s2 = np.asarray(fields["s2"], np.float32)[fluid].astype(np.float64)
+    strain = np.asarray(fields["strain"], np.float32)
+    sw = strain[near]
+    return (math.fsum(s2.tolist()), np.float32(strain[fluid].max() if fluid.any() else 0), int(near.sum()),
+            math.fsum(sw.astype(np.float64).tolist()), np.float32(sw.max() if sw.size else 0))
+
+
+def read_stress_state(filename: str, nx: int, ny: int):
+    """stress_state.dat (`x y sxx sxy syy strain near_wall obstacle`, y outer) back into
+    {"sxx", "sxy", "syy", "strain"}: float32[ny][nx], and "near_wall", "obstacle": uint8."""
+    t = np.loadtxt(filename, dtype=np.float64).reshape(ny, nx, 8)
+    out = {n: t[..., 2 + i].astype(np.float32) for i, n in enumerate(("sxx", "sxy", "syy", "strain"))}
+    out["near_wall"] = t[..., 6].astype(np.uint8)
+    out["obstacle"] = t[..., 7].astype(np.uint8)
     return out
 
 

@@ -76,6 +76,19 @@ GRAD_FIELDS = ("vorticity", "divergence", "strain", "q")
 GRAD_FIELDS3D = ("wx", "wy", "wz", "vorticity", "divergence", "strain", "q")
 # work shape of the D2Q9 gradient kernel (csrc/lbm_gradients.hpp): columns a wave owns, rows of a segment
 GRAD_STRIP_COLS, GRAD_SEGMENT_ROWS = 248, 32
+# every symbol include/lbm_stress_hip.h declares (non-equilibrium strain rate and wall shear; both engines)
+EXPORTED_STRESS = [
+    "lbm_store_stress", "lbm_store_stress_local", "lbm_stress_stats",
+    "lbm3d_store_stress", "lbm3d_store_stress_box", "lbm3d_stress_stats",
+]
+# index order of the output-pointer arrays (LBM_STRESS_* / LBM3D_STRESS_*)
+STRESS_FIELDS = ("sxx", "sxy", "syy", "strain")
+STRESS_FIELDS3D = ("sxx", "syy", "szz", "sxy", "sxz", "syz", "strain")
+# work units of the strain-rate kernels (csrc/lbm_stress.hpp).  D2Q9: cells of a lane's quad, and
+# consecutive quads (row-major over ceil(w / 4) quads per row) a block owns.  D3Q19: cells along x,
+# rows and planes a block owns on the 16-B path (one cell per lane: STRESS3D_BLOCK[0] / 4 along x).
+STRESS_QUAD, STRESS_BLOCK_QUADS = 4, 2048
+STRESS3D_BLOCK = (256, 4, 8)
 Q3 = 19
 
 
@@ -244,6 +257,12 @@ def load_library() -> ctypes.CDLL:
         "lbm3d_store_gradients": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
         "lbm3d_store_gradients_box": ([H, ctypes.POINTER(Box3D), ctypes.POINTER(f32p)], ctypes.c_int),
         "lbm3d_gradient_stats": ([H, f64p, f64p, f32p, f32p], ctypes.c_int),
+        "lbm_store_stress": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
+        "lbm_store_stress_local": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
+        "lbm_stress_stats": ([H, f64p, f32p, i64p, f64p, f32p], ctypes.c_int),
+        "lbm3d_store_stress": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
+        "lbm3d_store_stress_box": ([H, ctypes.POINTER(Box3D), ctypes.POINTER(f32p)], ctypes.c_int),
+        "lbm3d_stress_stats": ([H, f64p, f32p, i64p, f64p, f32p], ctypes.c_int),
         "lbm3d_total_free_cells": ([H], i64),
         "lbm3d_local_slabs": ([H, i32p, i32p, i32, i32p], ctypes.c_int),
         "lbm3d_last_error": ([H], ctypes.c_char_p),
@@ -483,12 +502,86 @@ class _Gradients:
         return w2.value, s2.value, mw.value, md.value
 
 
-class Engine(_WallForces, _Averages, _Gradients):
+class _Stress:
+    """Engine / Engine3D methods over include/lbm_stress_hip.h; the class sets
+    _FORCE_PREFIX ("lbm_" / "lbm3d_"), _force_shape() and _STRESS_FIELDS."""
+
+    def _stress_which(self, which):
+        names = self._STRESS_FIELDS
+        which = names if which is None else tuple(which)
+        bad = [n for n in which if n not in names]
+        if bad or len(set(which)) != len(which):
+            raise ValueError(f"strain-rate fields are a subset of {names}, each at most once; got {which}")
+        return which
+
+    def _stress_ptrs(self, out):
+        ptrs = (ctypes.POINTER(ctypes.c_float) * len(self._STRESS_FIELDS))()
+        for i, n in enumerate(self._STRESS_FIELDS):
+            if n in out:
+                ptrs[i] = _f32(out[n])
+        return ptrs
+
+    def strain_rate(self, which=None):
+        """{name: float32 array} of the requested strain-rate components and "strain"
+        (D2Q9: "sxx", "sxy", "syy"; D3Q19 also "szz", "sxz", "syz"), from the
+        non-equilibrium moments of the current lattice on the device (lbm_store_stress):
+        lio.neq_strain[3d] of store()'s cells, bit for bit.  Default: every field."""
+        which = self._stress_which(which)
+        out = {n: np.zeros(self._force_shape(), np.float32) for n in which}
+        self._check(getattr(self._L, self._FORCE_PREFIX + "store_stress")(self._h, self._stress_ptrs(out)))
+        return out
+
+    def strain_stats(self):
+        """(sum_s2, max_strain, wall_cells, sum_wall_strain, max_wall_strain) over this
+        handle's fluid cells (lbm_stress_stats); the last three over the fluid cells with a
+        blocked lattice neighbour.  Dissipation = 2 nu sum_s2; in simple shear the wall
+        shear stress is rho nu sqrt(2) strain."""
+        s2, sw = ctypes.c_double(), ctypes.c_double()
+        ms, mw = ctypes.c_float(), ctypes.c_float()
+        nw = ctypes.c_int64()
+        self._check(getattr(self._L, self._FORCE_PREFIX + "stress_stats")(
+            self._h, ctypes.byref(s2), ctypes.byref(ms), ctypes.byref(nw), ctypes.byref(sw), ctypes.byref(mw)))
+        return s2.value, ms.value, nw.value, sw.value, mw.value
+
+
+class Engine(_WallForces, _Averages, _Gradients, _Stress):
     """One lbm_handle: the HIP counterpart of the reference's poplar::Engine."""
 
     _FORCE_PREFIX = "lbm_"
     _AVG_FIELDS = AVG_FIELDS
     _GRAD_FIELDS = GRAD_FIELDS
+    _STRESS_FIELDS = STRESS_FIELDS
+
+    def strain_rate_local(self, which=None):
+        """[{name: float32[h][w]}] per local rect (local_rects() order; lbm_store_stress_local)."""
+        which = self._stress_which(which)
+        rects = self.local_rects()
+        n = int(self._L.lbm_local_cells(self._h))
+        packed = {f: np.zeros(n, np.float32) for f in which}
+        self._check(self._L.lbm_store_stress_local(self._h, self._stress_ptrs(packed)))
+        out, off = [], 0
+        for (_, _, w, h) in rects:
+            out.append({f: packed[f][off:off + w * h].reshape(h, w) for f in which})
+            off += w * h
+        return out
+
+    def strain_history(self, steps: int, every: int, accelerate_first: bool = False):
+        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and sample
+        strain_stats() after each chunk.  Returns (samples, av_vels): samples is a list of
+        (step, sum_s2, max_strain, wall_cells, sum_wall_strain, max_wall_strain), av_vels the
+        float32[steps] concatenation of the chunks' average velocities.  Chunking behaves
+        as in force_history."""
+        steps, every = int(steps), int(every)
+        if steps < 0 or every < 1:
+            raise ValueError("steps >= 0 and every >= 1")
+        samples, av, done = [], [], 0
+        while done < steps:
+            n = min(every, steps - done)
+            self.run_steps(n, accelerate_first and done == 0)
+            av.append(self.store(cells=False, n_av=n)[1].copy())
+            done += n
+            samples.append((done,) + self.strain_stats())
+        return samples, (np.concatenate(av) if av else np.zeros(0, np.float32))
 
     def gradients_local(self, which=None):
         """[{name: float32[h][w]}] per local rect (local_rects() order; lbm_store_gradients_local)."""
@@ -767,12 +860,37 @@ class Engine(_WallForces, _Averages, _Gradients):
             pass
 
 
-class Engine3D(_WallForces, _Averages, _Gradients):
+class Engine3D(_WallForces, _Averages, _Gradients, _Stress):
     """One lbm3d_handle: the D3Q19 extension engine (include/lbm3d_hip.h)."""
 
     _FORCE_PREFIX = "lbm3d_"
     _AVG_FIELDS = AVG_FIELDS3D
     _GRAD_FIELDS = GRAD_FIELDS3D
+    _STRESS_FIELDS = STRESS_FIELDS3D
+
+    def strain_rate_box(self, x0: int, y0: int, z0: int, nx: int, ny: int, nz: int, which=None):
+        """{name: float32[nz][ny][nx]} of the cells [x0, x0+nx) x [y0, y0+ny) x [z0, z0+nz)
+        (lbm3d_store_stress_box); a box that is empty or leaves the domain raises LbmError."""
+        which = self._stress_which(which)
+        box = Box3D(int(x0), int(y0), int(z0), int(nx), int(ny), int(nz))
+        out = {n: np.zeros((max(box.nz, 0), max(box.ny, 0), max(box.nx, 0)), np.float32) for n in which}
+        self._check(self._L.lbm3d_store_stress_box(self._h, ctypes.byref(box), self._stress_ptrs(out)))
+        return out
+
+    def strain_history(self, steps: int, every: int):
+        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and sample
+        strain_stats() after each chunk: a list of (step, sum_s2, max_strain, wall_cells,
+        sum_wall_strain, max_wall_strain)."""
+        steps, every = int(steps), int(every)
+        if steps < 0 or every < 1:
+            raise ValueError("steps >= 0 and every >= 1")
+        samples, done = [], 0
+        while done < steps:
+            n = min(every, steps - done)
+            self.run_steps(n)
+            done += n
+            samples.append((done,) + self.strain_stats())
+        return samples
 
     def gradients_box(self, x0: int, y0: int, z0: int, nx: int, ny: int, nz: int, which=None):
         """{name: float32[nz][ny][nx]} of the cells [x0, x0+nx) x [y0, y0+ny) x [z0, z0+nz)
