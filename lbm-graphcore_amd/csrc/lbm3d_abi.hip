@@ -1,11 +1,13 @@
 // lbm3d_abi.hip -- the extern "C" functions of include/lbm3d_hip.h,
 // include/lbm3d_fields_hip.h and the D3Q19 functions of
 // include/lbm_forces_hip.h, include/lbm_averages_hip.h and
-// include/lbm_gradients_hip.h and include/lbm_stress_hip.h over the engine
+// include/lbm_gradients_hip.h, include/lbm_stress_hip.h and
+// include/lbm_binned_hip.h over the engine
 // (lbm3d_engine.hpp), and the posting order of its RCCL ghost exchange.
 
 #include "lbm3d_engine.hpp"
 #include "lbm_averages_hip.h"
+#include "lbm_binned_hip.h"
 #include "lbm_gradients_hip.h"
 #include "lbm_stress_hip.h"
 
@@ -163,6 +165,16 @@ int lbm3d_stress_stats(lbm3d_handle *h, double *sum_s2, float *max_strain, int64
                        double *sum_wall_strain, float *max_wall_strain) {
     if (!h) return LBM_E_INVALID;
     return guarded(h, [&] { h->stress_stats(sum_s2, max_strain, wall_cells, sum_wall_strain, max_wall_strain); });
+}
+
+int lbm3d_store_binned(lbm3d_handle *h, int32_t bw, int32_t bh, int32_t bd, double *const out[LBM3D_BIN_FIELDS]) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->store_binned(bw, bh, bd, out); });
+}
+
+int lbm3d_bin_fluid_cells(lbm3d_handle *h, int32_t bw, int32_t bh, int32_t bd, int64_t *count) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->bin_fluid_cells(bw, bh, bd, count); });
 }
 
 int lbm3d_last_run_seconds(lbm3d_handle *h, double *seconds) {

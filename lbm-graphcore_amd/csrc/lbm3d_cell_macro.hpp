@@ -16,6 +16,13 @@ struct Cell3Macro {
     float ux, uy, uz, u, pressure;
 };
 
+// the momentum (rho u_x, rho u_y, rho u_z): the numerators cell3_macro divides by rho
+__device__ __forceinline__ void cell3_momentum(const float (&s)[19], float &jx, float &jy, float &jz) {
+    jx = (s[1] + s[5] + s[7] + s[10] + s[16]) - (s[2] + s[6] + s[8] + s[11] + s[15]);
+    jy = (s[3] + s[5] + s[8] + s[12] + s[18]) - (s[4] + s[6] + s[7] + s[13] + s[17]);
+    jz = (s[9] + s[10] + s[11] + s[12] + s[13]) - (s[14] + s[15] + s[16] + s[17] + s[18]);
+}
+
 // NEED_V: a velocity component or |u| wanted (three divides); NEED_U: |u| wanted (sqrt); rho is always formed
 template <bool NEED_V, bool NEED_U>
 __device__ __forceinline__ Cell3Macro cell3_macro(const float (&s)[19], bool blocked, float obst_pressure,
@@ -26,9 +33,11 @@ __device__ __forceinline__ Cell3Macro cell3_macro(const float (&s)[19], bool blo
     Cell3Macro m{0.f, 0.f, 0.f, 0.f, obst_pressure};
     if (blocked) return m;
     if (NEED_V) {
-        m.ux = ((s[1] + s[5] + s[7] + s[10] + s[16]) - (s[2] + s[6] + s[8] + s[11] + s[15])) / rho;
-        m.uy = ((s[3] + s[5] + s[8] + s[12] + s[18]) - (s[4] + s[6] + s[7] + s[13] + s[17])) / rho;
-        m.uz = ((s[9] + s[10] + s[11] + s[12] + s[13]) - (s[14] + s[15] + s[16] + s[17] + s[18])) / rho;
+        float jx, jy, jz;
+        cell3_momentum(s, jx, jy, jz);
+        m.ux = jx / rho;
+        m.uy = jy / rho;
+        m.uz = jz / rho;
     }
     if (NEED_U) m.u = sqrtf(m.ux * m.ux + m.uy * m.uy + m.uz * m.uz);
     m.pressure = rho * (1.f / 3.f);

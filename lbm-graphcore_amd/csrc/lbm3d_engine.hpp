@@ -9,6 +9,7 @@
 //   lbm3d_averages.hip time-averaged fields and Reynolds stresses (kernels + host side);
 //   lbm3d_gradients.hip vorticity, divergence, strain rate and Q (kernel + host side);
 //   lbm3d_stress.hip   strain rate and wall shear from the non-equilibrium moments (kernel + host side);
+//   lbm3d_binned.hip   sums over box-shaped bins of the current lattice (kernel + host side);
 //   lbm3d_abi.hip      the extern "C" functions and the RCCL posting order.
 #pragma once
 
@@ -257,4 +258,7 @@ struct lbm3d_handle {
     void store_stress_box(const lbm3d_box &b, float *const *host);
     void stress_stats(double *sum_s2, float *max_strain, int64_t *wall_cells, double *sum_wall_strain,
                       float *max_wall_strain);
+    // lbm3d_binned.hip (include/lbm_binned_hip.h)
+    void store_binned(int bw, int bh, int bd, double *const *out);
+    void bin_fluid_cells(int bw, int bh, int bd, int64_t *count);
 };

@@ -1,8 +1,10 @@
 // lbm_abi.hip -- the extern "C" functions of include/lbm_hip.h and the D2Q9
 // functions of include/lbm_forces_hip.h, include/lbm_averages_hip.h and
-// include/lbm_gradients_hip.h and include/lbm_stress_hip.h over the engine.
+// include/lbm_gradients_hip.h, include/lbm_stress_hip.h and
+// include/lbm_binned_hip.h over the engine.
 
 #include "lbm_averages_hip.h"
+#include "lbm_binned_hip.h"
 #include "lbm_engine.hpp"
 #include "lbm_forces_hip.h"
 #include "lbm_gradients_hip.h"
@@ -247,6 +249,16 @@ int lbm_stress_stats(lbm_handle *h, double *sum_s2, float *max_strain, int64_t *
                      float *max_wall_strain) {
     if (!h) return LBM_E_INVALID;
     return guarded(h, [&] { h->stress_stats(sum_s2, max_strain, wall_cells, sum_wall_strain, max_wall_strain); });
+}
+
+int lbm_store_binned(lbm_handle *h, int32_t bw, int32_t bh, double *const out[LBM_BIN_FIELDS]) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->store_binned(bw, bh, out); });
+}
+
+int lbm_bin_fluid_cells(lbm_handle *h, int32_t bw, int32_t bh, int64_t *count) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->bin_fluid_cells(bw, bh, count); });
 }
 
 int64_t lbm_local_cells(lbm_handle *h) {

@@ -16,6 +16,12 @@ struct CellMacro {
     float ux, uy, u, pressure;
 };
 
+// the momentum (rho u_x, rho u_y): the numerators cell_macro divides by rho
+__device__ __forceinline__ void cell_momentum(const float (&c)[9], float &jx, float &jy) {
+    jx = c[1] + c[5] + c[8] - (c[3] + c[6] + c[7]);
+    jy = c[2] + c[5] + c[6] - (c[4] + c[7] + c[8]);
+}
+
 // need_v: u_x / u_y wanted (two divides); need_u: |u| wanted (sqrt); rho is always formed
 template <bool NEED_V, bool NEED_U>
 __device__ __forceinline__ CellMacro cell_macro(const float (&c)[9], bool blocked, float obst_pressure, float &rho) {
@@ -25,8 +31,10 @@ __device__ __forceinline__ CellMacro cell_macro(const float (&c)[9], bool blocke
     CellMacro m{0.f, 0.f, 0.f, obst_pressure};
     if (blocked) return m;
     if (NEED_V) {
-        m.ux = (c[1] + c[5] + c[8] - (c[3] + c[6] + c[7])) / rho;
-        m.uy = (c[2] + c[5] + c[6] - (c[4] + c[7] + c[8])) / rho;
+        float jx, jy;
+        cell_momentum(c, jx, jy);
+        m.ux = jx / rho;
+        m.uy = jy / rho;
     }
     if (NEED_U) m.u = sqrtf((m.ux * m.ux) + (m.uy * m.uy));
     m.pressure = rho * (1.f / 3.f);

@@ -12,6 +12,8 @@
 //                         current lattice (kernels and their host side);
 //   lbm_stress.hip        strain rate and wall shear from the non-equilibrium
 //                         moments of the current lattice (kernel and its host side);
+//   lbm_binned.hip        sums over rectangular bins of the current lattice
+//                         (kernels and their host side);
 //   lbm_exchange.hip      partition rule, torus neighbours, halo destinations,
 //                         the posted exchange (RCCL or device copies);
 //   lbm_split.hip         work decomposition: boundary / interior split,
@@ -439,5 +441,8 @@ struct lbm_handle {
     void store_stress(float *const *out, bool local = false);
     void stress_stats(double *sum_s2, float *max_strain, int64_t *wall_cells, double *sum_wall_strain,
                       float *max_wall_strain);
+    // binned sums (lbm_binned.hip; include/lbm_binned_hip.h)
+    void store_binned(int bw, int bh, double *const *out);
+    void bin_fluid_cells(int bw, int bh, int64_t *count);
     void destroy();
 };

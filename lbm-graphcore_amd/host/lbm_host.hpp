@@ -422,6 +422,56 @@ inline bool writeStressState(const std::string &filename, const Params &p, const
     return true;
 }
 
+// ---- binned sums (include/lbm_binned_hip.h) ----
+
+// The nine LBM_BIN_* sums and the fluid cells per bin of bw x bh cells, planar
+// [nby][nbx]: per bin the fp64 sum, row after row, of (double) of the header's
+// fp32 terms over the bin's fluid cells (products formed in fp64).
+struct BinnedSums {
+    size_t nbx = 0, nby = 0;
+    std::vector<double> sum[9];
+    std::vector<int64_t> fluid;
+};
+
+inline BinnedSums binnedSums(const Params &p, const Obstacles &o, const std::vector<float> &cells, size_t bw,
+                             size_t bh) {
+    BinnedSums r;
+    r.nbx = (p.nx + bw - 1) / bw;
+    r.nby = (p.ny + bh - 1) / bh;
+    for (auto &a : r.sum) a.assign(r.nbx * r.nby, 0.0);
+    r.fluid.assign(r.nbx * r.nby, 0);
+    for (size_t y = 0; y < p.ny; ++y)
+        for (size_t x = 0; x < p.nx; ++x) {
+            if (o.at(x, y)) continue;
+            const float *c = &cells[(x + y * p.nx) * NumSpeeds];
+            const Macro m = macroscopic(p, o, cells, x, y);
+            float rho = 0.f;
+            for (unsigned k = 0; k < NumSpeeds; ++k) rho += c[k];
+            const float jx = c[1] + c[5] + c[8] - (c[3] + c[6] + c[7]);
+            const float jy = c[2] + c[5] + c[6] - (c[4] + c[7] + c[8]);
+            const double ux = m.ux, uy = m.uy;
+            const double t[9] = {rho, jx, jy, ux, uy, m.u, ux * ux, ux * uy, uy * uy};
+            const size_t b = x / bw + (y / bh) * r.nbx;
+            for (int k = 0; k < 9; ++k) r.sum[k][b] += t[k];
+            ++r.fluid[b];
+        }
+    return r;
+}
+
+// binned_state.dat: `bx by fluid` and the nine sums per bin, by outer
+inline bool writeBinnedState(const std::string &filename, const BinnedSums &b) {
+    FILE *file = fopen(filename.c_str(), "w");
+    if (!file) return false;
+    for (size_t by = 0; by < b.nby; ++by)
+        for (size_t bx = 0; bx < b.nbx; ++bx) {
+            const size_t i = bx + by * b.nbx;
+            fprintf(file, "%zu %zu %lld", bx, by, (long long)b.fluid[i]);
+            for (const auto &a : b.sum) fprintf(file, " %.12E", a[i]);
+            fprintf(file, "\n");
+        }
+    return fclose(file) == 0;
+}
+
 // forces.dat: `body fx fy links` per body, then `total fx fy links`
 inline bool writeForces(const std::string &filename, const BodyForces &f) {
     FILE *file = fopen(filename.c_str(), "w");

@@ -3,7 +3,7 @@
 //
 //   lbm_runner --params P --obstacles O [-n N] [--device gpu|loopback|cpu] [-d] [--exe ignored]
 //              [--runs 5] [--kernel auto|resident|stream|step2|vec4|scalar|pipeline] [--spl S] [--out-dir DIR]
-//              [--tolerance] [--device-fields] [--forces] [--mean-every N] [--gradients] [--stress]
+//              [--tolerance] [--device-fields] [--forces] [--mean-every N] [--gradients] [--stress] [--binned BWxBH]
 //              [--json FILE]
 //
 // Flow (same program numbering as the reference):
@@ -38,6 +38,11 @@
 // near_wall obstacle` per cell, the values in final_state.dat's format
 // (lbm_stress_hip.h) -- from lbm_store_stress on the GPU, from
 // lbmhost::neqStrain of the stored cells with --device cpu.
+// --binned BWxBH writes binned_state.dat after the run: one row per bin of
+// BW x BH cells, `bx by fluid` and the nine sums rho jx jy ux uy speed uxux
+// uxuy uyuy in %.12E (lbm_binned_hip.h) -- from lbm_store_binned and
+// lbm_bin_fluid_cells on the GPU, from lbmhost::binnedSums of the stored cells
+// with --device cpu.
 // --device loopback places all N sub-domains on GPU 0 (the emulator analogue
 // of --device ipumodel: exercises the multi-GPU halo path on one device).
 // --device cpu runs the same fused step on the host's cores (lbm_cpu.hpp:
@@ -56,6 +61,7 @@
 #include <vector>
 
 #include "lbm_averages_hip.h"
+#include "lbm_binned_hip.h"
 #include "lbm_cpu.hpp"
 #include "lbm_forces_hip.h"
 #include "lbm_gradients_hip.h"
@@ -91,6 +97,9 @@ void usage(const char *exe) {
               << "                       the Q criterion (Okubo-Weiss) of the final state\n"
               << "      --stress         also write stress_state.dat: the strain-rate tensor and its magnitude from the\n"
               << "                       non-equilibrium moments of the final state, and the near-wall cells\n"
+              << "      --binned arg     BWxBH: also write binned_state.dat: per bin of BW x BH cells the fluid cells and\n"
+              << "                       the fp64 sums of rho, rho u, u, |u| and the velocity products of the final state\n"
+              << "                       (e.g. NXx1: the profile across the channel; 1xNY: the flux through each section)\n"
               << "      --out-dir arg    directory for av_vels.dat / final_state.dat (default: .)\n"
               << "      --graph-steps arg  replay the step loop as hipGraphs of 2*arg launches (0 = library default, <0 = off)\n"
               << "      --dump-partitioning arg  write the sub-domain decomposition as JSON\n"
@@ -112,7 +121,7 @@ std::string json_str(const std::string &v) {
 
 // --device cpu: the reference's program sequence on the host backend
 int run_cpu(const lbmhost::Params &params, const lbmhost::Obstacles &obstacles, const std::string &outDir, int runs,
-            bool forces, bool gradients, bool stress) {
+            bool forces, bool gradients, bool stress, int binW, int binH) {
     std::cout << "Running on the host CPU (" << lbmcpu::Engine::threads()
               << " threads; bitwise numerics: the reference's LastChance.cpp arithmetic)" << std::endl;
     auto cells = lbmhost::initialiseCells(params);
@@ -148,6 +157,9 @@ int run_cpu(const lbmhost::Params &params, const lbmhost::Obstacles &obstacles, 
             lbmhost::writeStressState(outDir + "/stress_state.dat", params, obstacles, strain,
                                       lbmhost::nearWall(obstacles));
         }
+        if (binW > 0)
+            lbmhost::writeBinnedState(outDir + "/binned_state.dat",
+                                      lbmhost::binnedSums(params, obstacles, cells, (size_t)binW, (size_t)binH));
     });
     std::cout << "==done==" << std::endl;
     std::cout << "Total compute time was \t" << std::right << std::setw(12) << std::setprecision(5)
@@ -177,7 +189,7 @@ int main(int argc, char *argv[]) {
     std::string paramsFile, obstaclesFile, device = "gpu", exeFile, kernel = "auto", outDir = ".", dumpFile, jsonFile;
     std::vector<std::string> gpuOnly;  // GPU-only options given on the command line
     int spl = 0;
-    int numGpus = 1, runs = 5, graphSteps = 0, meanEvery = 0;
+    int numGpus = 1, runs = 5, graphSteps = 0, meanEvery = 0, binW = 0, binH = 0;
     bool debug = false, tolerance = false, deviceFields = false, forces = false, gradients = false, stress = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -235,6 +247,8 @@ int main(int argc, char *argv[]) {
             gradients = true;
         } else if (a == "--stress") {
             stress = true;
+        } else if (a == "--binned") {
+            if (!next(v) || sscanf(v.c_str(), "%dx%d", &binW, &binH) != 2) { usage(argv[0]); return EXIT_FAILURE; }
         } else if (a == "--mean-every") {
             if (!next(v)) { usage(argv[0]); return EXIT_FAILURE; }
             meanEvery = std::atoi(v.c_str());
@@ -275,6 +289,12 @@ int main(int argc, char *argv[]) {
         std::cerr << "Could not parse obstacles file" << std::endl;
         return EXIT_FAILURE;
     }
+    if (binW != 0 || binH != 0) {
+        if (binW < 1 || binH < 1 || (size_t)binW > params->nx || (size_t)binH > params->ny) {
+            std::cerr << "--binned: bin sizes must lie in 1..nx and 1..ny" << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
     if (!dumpFile.empty()) {
         // partitioning.json in the layout of grids::serializeToJson
         // (StructuredGridUtils.hpp:135-158), one entry per GPU sub-domain;
@@ -311,7 +331,7 @@ int main(int argc, char *argv[]) {
             std::cerr << " (the host backend runs the reference arithmetic on one domain)" << std::endl;
             return EXIT_FAILURE;
         }
-        return run_cpu(*params, *obstacles, outDir, runs, forces, gradients, stress);
+        return run_cpu(*params, *obstacles, outDir, runs, forces, gradients, stress, binW, binH);
     }
     const int ndev = lbm_device_count();
     if (ndev <= 0) {
@@ -387,6 +407,7 @@ int main(int argc, char *argv[]) {
     lbmhost::BodyForces bodyForces;                   // --forces: forces.dat
     std::vector<float> grads[LBM_GRAD_FIELDS];        // --gradients: gradient_state.dat's columns, planar
     std::vector<float> strain[LBM_STRESS_FIELDS];     // --stress: stress_state.dat's columns, planar
+    lbmhost::BinnedSums binned;                       // --binned: binned_state.dat
     lbmhost::timedStep("Running copy to host step", [&]() {
         if (deviceFields) {
             const size_t n = params->nx * params->ny;
@@ -424,6 +445,18 @@ int main(int argc, char *argv[]) {
             }
             lbmhost::check(lbm_store_stress(h, out), h, "lbm_store_stress");
         }
+        if (binW > 0) {
+            binned.nbx = LBM_BIN_COUNT(params->nx, (size_t)binW);
+            binned.nby = LBM_BIN_COUNT(params->ny, (size_t)binH);
+            double *out[LBM_BIN_FIELDS];
+            for (int f = 0; f < LBM_BIN_FIELDS; ++f) {
+                binned.sum[f].assign(binned.nbx * binned.nby, 0.0);
+                out[f] = binned.sum[f].data();
+            }
+            binned.fluid.assign(binned.nbx * binned.nby, 0);
+            lbmhost::check(lbm_store_binned(h, binW, binH, out), h, "lbm_store_binned");
+            lbmhost::check(lbm_bin_fluid_cells(h, binW, binH, binned.fluid.data()), h, "lbm_bin_fluid_cells");
+        }
         if (forces) {
             std::vector<int32_t> labels;
             const int32_t nbodies = lbmhost::labelBodies(*obstacles, labels);
@@ -445,6 +478,7 @@ int main(int argc, char *argv[]) {
         if (stress)
             lbmhost::writeStressState(outDir + "/stress_state.dat", *params, *obstacles, strain,
                                       lbmhost::nearWall(*obstacles));
+        if (binW > 0) lbmhost::writeBinnedState(outDir + "/binned_state.dat", binned);
         if (!means[0].empty()) lbmhost::writeMeanState(outDir + "/mean_state.dat", *params, *obstacles, means);
         lbmhost::writeAverageVelocities(outDir + "/av_vels.dat", av_vels);
         if (deviceFields)

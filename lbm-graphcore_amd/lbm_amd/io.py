@@ -16,6 +16,9 @@
 * neq_strain, neq_strain3d, near_wall, near_wall3d, strain_stats
                         -- the non-equilibrium strain rate of include/lbm_stress_hip.h in fp32
                            numpy (Engine.strain_rate(), .strain_stats())
+* binned_terms, binned_sums (+ ...3d), bin_reduce, binned_means
+                        -- the binned sums of include/lbm_binned_hip.h: the per-cell terms in
+                           numpy, math.fsum per bin (Engine.binned(), .profile_y(), .flux_x())
 
 Error behaviour follows the reference: loaders return None (std::nullopt)
 and print the reference's message on stderr.  One deliberate strengthening:
@@ -527,6 +530,129 @@ def read_stress_state(filename: str, nx: int, ny: int):
     out = {n: t[..., 2 + i].astype(np.float32) for i, n in enumerate(("sxx", "sxy", "syy", "strain"))}
     out["near_wall"] = t[..., 6].astype(np.uint8)
     out["obstacle"] = t[..., 7].astype(np.uint8)
+    return out
+
+
+# ---- binned sums (include/lbm_binned_hip.h) ----
+
+# index order of LBM_BIN_* / LBM3D_BIN_*
+BIN_FIELDS = ("rho", "jx", "jy", "ux", "uy", "speed", "uxux", "uxuy", "uyuy")
+BIN_FIELDS3D = ("rho", "jx", "jy", "jz", "ux", "uy", "uz", "speed",
+                "uxux", "uxuy", "uxuz", "uyuy", "uyuz", "uzuz")
+
+
+def _bin_products(t, names):
+    for a in range(len(names)):
+        for b in range(a, len(names)):
+            t[names[a] + names[b]] = t[names[a]] * t[names[b]]   # float64: exact
+
+
+def binned_terms(p: Params, obstacles: np.ndarray, cells: np.ndarray):
+    """{name: float64[ny][nx]} of the per-cell terms the D2Q9 binned sums add, in
+    BIN_FIELDS order: (double) of macroscopic()'s fp32 ux, uy, speed, of its sequential
+    fp32 density and of the fp32 numerators jx, jy it divides by the density, and the
+    fp64 products of the velocities.  +0 on obstacle cells."""
+    c = cells.astype(np.float32, copy=False)
+    ux, uy, u, _ = macroscopic(p, obstacles, cells)
+    rho = np.zeros(c.shape[:2], np.float32)
+    for k in range(Q):
+        rho = rho + c[..., k]
+    jx = ((c[..., 1] + c[..., 5]) + c[..., 8]) - ((c[..., 3] + c[..., 6]) + c[..., 7])
+    jy = ((c[..., 2] + c[..., 5]) + c[..., 6]) - ((c[..., 4] + c[..., 7]) + c[..., 8])
+    fluid = ~np.asarray(obstacles).reshape(rho.shape).astype(bool)
+    t = {n: np.where(fluid, f, np.float32(0)).astype(np.float64)
+         for n, f in (("rho", rho), ("jx", jx), ("jy", jy), ("ux", ux), ("uy", uy), ("speed", u))}
+    _bin_products(t, ("ux", "uy"))
+    return {n: t[n] for n in BIN_FIELDS}
+
+
+def binned_terms3d(p: Params3D, obstacles: np.ndarray, cells: np.ndarray):
+    """The same for D3Q19: {name: float64[nz][ny][nx]} in BIN_FIELDS3D order, from
+    macroscopic3d()'s values."""
+    c = cells.astype(np.float32, copy=False)
+
+    def seq(*ks):
+        acc = c[..., ks[0]]
+        for k in ks[1:]:
+            acc = acc + c[..., k]
+        return acc
+
+    ux, uy, uz, u, _ = macroscopic3d(p, obstacles, cells)
+    rho = seq(*range(19))
+    jx = seq(1, 5, 7, 10, 16) - seq(2, 6, 8, 11, 15)
+    jy = seq(3, 5, 8, 12, 18) - seq(4, 6, 7, 13, 17)
+    jz = seq(9, 10, 11, 12, 13) - seq(14, 15, 16, 17, 18)
+    fluid = ~np.asarray(obstacles).reshape(rho.shape).astype(bool)
+    t = {n: np.where(fluid, f, np.float32(0)).astype(np.float64)
+         for n, f in (("rho", rho), ("jx", jx), ("jy", jy), ("jz", jz), ("ux", ux), ("uy", uy), ("uz", uz),
+                      ("speed", u))}
+    _bin_products(t, ("ux", "uy", "uz"))
+    return {n: t[n] for n in BIN_FIELDS3D}
+
+
+def bin_reduce(a: np.ndarray, bins, exact: bool = True) -> np.ndarray:
+    """Sum `a` over the cells of each bin.  bins = (bw, bh[, bd]) in cells along x, y[, z];
+    `a` is indexed [[z]][y][x].  Bins tile the array from its first cell and the last one
+    along an axis may be ragged.  exact: math.fsum per bin (the exactly rounded sum of
+    float64 terms, from +0.0: a sum of value zero is +0.0 whatever the signs of its zero
+    terms); otherwise numpy's sum in a's own type (integer counts)."""
+    import math
+    a = np.asarray(a)
+    sizes = tuple(int(b) for b in bins)[::-1]        # slowest axis first, as a's
+    if len(sizes) != a.ndim or any(b < 1 for b in sizes):
+        raise ValueError("one bin size >= 1 per axis")
+    counts = tuple(-(-n // b) for n, b in zip(a.shape, sizes))
+    out = np.zeros(counts, np.float64 if exact else a.dtype)
+    if all(b == 1 for b in sizes):                    # one-cell bins: the cell itself
+        out[...] = a
+        return out + 0.0 if exact else out
+    for idx in np.ndindex(*counts):
+        block = a[tuple(slice(i * b, (i + 1) * b) for i, b in zip(idx, sizes))]
+        out[idx] = math.fsum(block.ravel().tolist()) + 0.0 if exact else block.sum()
+    return out
+
+
+def _binned(terms, obstacles, bins):
+    out = {n: bin_reduce(t, bins) for n, t in terms.items()}
+    shape = next(iter(terms.values())).shape
+    fluid = (~np.asarray(obstacles).reshape(shape).astype(bool)).astype(np.int64)
+    out["fluid"] = bin_reduce(fluid, bins, exact=False)
+    return out
+
+
+def binned_sums(p: Params, obstacles: np.ndarray, cells: np.ndarray, bw: int, bh: int):
+    """The definition of lbm_store_binned restated: {name: float64[nby][nbx]} for the
+    BIN_FIELDS -- per bin the exactly rounded sum (math.fsum) of binned_terms() over its
+    fluid cells, +0 over none -- and "fluid": int64, the fluid cells per bin."""
+    return _binned(binned_terms(p, obstacles, cells), obstacles, (bw, bh))
+
+
+def binned_sums3d(p: Params3D, obstacles: np.ndarray, cells: np.ndarray, bw: int, bh: int, bd: int):
+    """The same for D3Q19 (lbm3d_store_binned): float64[nbz][nby][nbx] per BIN_FIELDS3D
+    name, and "fluid"."""
+    return _binned(binned_terms3d(p, obstacles, cells), obstacles, (bw, bh, bd))
+
+
+def binned_means(sums):
+    """{name: sum / fluid} of a dict binned_sums / Engine.binned returns (0 where a bin
+    holds no fluid cell); "fluid" is passed through."""
+    fluid = np.asarray(sums["fluid"])
+    out = {}
+    for n, s in sums.items():
+        if n == "fluid":
+            out[n] = fluid
+            continue
+        s = np.asarray(s, np.float64)
+        out[n] = np.divide(s, fluid, out=np.zeros_like(s), where=fluid != 0)
+    return out
+
+
+def read_binned_state(filename: str, nbx: int, nby: int):
+    """binned_state.dat (`bx by fluid` and the nine BIN_FIELDS sums, by outer) back into
+    {name: float64[nby][nbx]} and "fluid": int64."""
+    t = np.loadtxt(filename, dtype=np.float64).reshape(nby, nbx, 3 + len(BIN_FIELDS))
+    out = {n: t[..., 3 + i].copy() for i, n in enumerate(BIN_FIELDS)}
+    out["fluid"] = t[..., 2].astype(np.int64)
     return out
 
 

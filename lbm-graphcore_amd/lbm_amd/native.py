@@ -89,6 +89,17 @@ STRESS_FIELDS3D = ("sxx", "syy", "szz", "sxy", "sxz", "syz", "strain")
 # rows and planes a block owns on the 16-B path (one cell per lane: STRESS3D_BLOCK[0] / 4 along x).
 STRESS_QUAD, STRESS_BLOCK_QUADS = 4, 2048
 STRESS3D_BLOCK = (256, 4, 8)
+# every symbol include/lbm_binned_hip.h declares (sums over rectangular bins; both engines)
+EXPORTED_BINNED = ["lbm_store_binned", "lbm_bin_fluid_cells", "lbm3d_store_binned", "lbm3d_bin_fluid_cells"]
+# index order of the output-pointer arrays (LBM_BIN_* / LBM3D_BIN_*)
+BIN_FIELDS = ("rho", "jx", "jy", "ux", "uy", "speed", "uxux", "uxuy", "uyuy")
+BIN_FIELDS3D = ("rho", "jx", "jy", "jz", "ux", "uy", "uz", "speed",
+                "uxux", "uxuy", "uxuz", "uyuy", "uyuz", "uzuz")
+# work units of the binned-sum kernels (csrc/lbm_binned.hpp).  D2Q9: cells of a lane's quad, columns
+# of a wave, most rows of a chunk (a chunk never straddles a bin).  D3Q19: columns of a wave (one cell
+# per lane); a chunk is at most BIN_CHUNK_ROWS planes.
+BIN_QUAD, BIN_WAVE_COLS, BIN_CHUNK_ROWS = 4, 256, 32
+BIN3D_WAVE_COLS = 64
 Q3 = 19
 
 
@@ -263,6 +274,10 @@ def load_library() -> ctypes.CDLL:
         "lbm3d_store_stress": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
         "lbm3d_store_stress_box": ([H, ctypes.POINTER(Box3D), ctypes.POINTER(f32p)], ctypes.c_int),
         "lbm3d_stress_stats": ([H, f64p, f32p, i64p, f64p, f32p], ctypes.c_int),
+        "lbm_store_binned": ([H, i32, i32, ctypes.POINTER(f64p)], ctypes.c_int),
+        "lbm_bin_fluid_cells": ([H, i32, i32, i64p], ctypes.c_int),
+        "lbm3d_store_binned": ([H, i32, i32, i32, ctypes.POINTER(f64p)], ctypes.c_int),
+        "lbm3d_bin_fluid_cells": ([H, i32, i32, i32, i64p], ctypes.c_int),
         "lbm3d_total_free_cells": ([H], i64),
         "lbm3d_local_slabs": ([H, i32p, i32p, i32, i32p], ctypes.c_int),
         "lbm3d_last_error": ([H], ctypes.c_char_p),
@@ -544,13 +559,112 @@ class _Stress:
         return s2.value, ms.value, nw.value, sw.value, mw.value
 
 
-class Engine(_WallForces, _Averages, _Gradients, _Stress):
+class _Binned:
+    """Engine / Engine3D methods over include/lbm_binned_hip.h; the class sets
+    _FORCE_PREFIX ("lbm_" / "lbm3d_"), _force_shape() and _BIN_FIELDS."""
+
+    def _bin_which(self, which):
+        names = self._BIN_FIELDS
+        which = names if which is None else tuple(which)
+        bad = [n for n in which if n not in names]
+        if bad or len(set(which)) != len(which):
+            raise ValueError(f"binned fields are a subset of {names}, each at most once; got {which}")
+        return which
+
+    def _bin_shape(self, bins):
+        shape = self._force_shape()                      # slowest axis first
+        if len(bins) != len(shape):
+            raise ValueError(f"{len(shape)} bin sizes (x, y[, z]) expected; got {bins}")
+        return tuple(-(-n // max(int(b), 1)) for n, b in zip(shape, bins[::-1]))
+
+    def bin_fluid_cells(self, *bins):
+        """int64 array of the fluid cells per bin over this handle's sub-domains
+        (lbm_bin_fluid_cells).  The obstacle map never changes, so the result is kept
+        per bin shape."""
+        bins = tuple(int(b) for b in bins)
+        cache = self.__dict__.setdefault("_bin_fluid", {})
+        if bins not in cache:
+            count = np.zeros(self._bin_shape(bins), np.int64)
+            self._check(getattr(self._L, self._FORCE_PREFIX + "bin_fluid_cells")(
+                self._h, *bins, count.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+            cache[bins] = count
+        return cache[bins].copy()
+
+    def binned(self, *bins, which=None):
+        """{name: float64 array} of the sums of the requested per-cell quantities over
+        bins of bw x bh[ x bd] cells (binned(bw, bh[, bd])), formed on the device from
+        the current lattice (lbm_store_binned), and "fluid": the fluid cells per bin.
+        Arrays are [[nbz]][nby][nbx].  lio.binned_sums[3d] of store()'s cells restates
+        them; lio.binned_means divides.  Default: every field.  RCCL: this rank's partial
+        sums and counts over the full bin grid."""
+        bins = tuple(int(b) for b in bins)
+        which = self._bin_which(which)
+        out = {n: np.zeros(self._bin_shape(bins), np.float64) for n in which}
+        ptrs = (ctypes.POINTER(ctypes.c_double) * len(self._BIN_FIELDS))()
+        for i, n in enumerate(self._BIN_FIELDS):
+            if n in out:
+                ptrs[i] = out[n].ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        self._check(getattr(self._L, self._FORCE_PREFIX + "store_binned")(self._h, *bins, ptrs))
+        out["fluid"] = self.bin_fluid_cells(*bins)
+        return out
+
+    def _bin_means(self, bins, which):
+        s = self.binned(*bins, which=which)
+        fluid = s.pop("fluid")
+        return {n: np.divide(a, fluid, out=np.zeros_like(a), where=fluid != 0) for n, a in s.items()}
+
+    def profile_y(self, which=None):
+        """{name: float64[ny]}: the means over x (D3Q19: over x and z) of the requested
+        quantities per row y -- the profile across the channel.  Bins (nx, 1[, nz])."""
+        shape = self._force_shape()
+        bins = (shape[-1], 1) + ((shape[0],) if len(shape) == 3 else ())
+        return {n: a.reshape(-1) for n, a in self._bin_means(bins, which).items()}
+
+    def flux_x(self):
+        """float64[nx]: the sum of rho u_x over every cross-section x = const (the "jx"
+        sums of bins (1, ny[, nz])): the mass flux through it."""
+        shape = self._force_shape()
+        return self.binned(*((1,) + shape[::-1][1:]), which=("jx",))["jx"].reshape(-1)
+
+    def coarse_fields(self, k: int):
+        """{name: float64 array} of the k x k[ x k] block means of "ux", "uy"[, "uz"] and
+        "speed" over the fluid cells of each block (0 where a block holds none)."""
+        dims = len(self._force_shape())
+        which = ("ux", "uy", "uz", "speed") if dims == 3 else ("ux", "uy", "speed")
+        bins = tuple(min(int(k), n) for n in self._force_shape()[::-1])
+        return self._bin_means(bins, which)
+
+    def binned_history(self, steps: int, every: int, *bins, which=None):
+        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and take
+        binned(*bins, which) after each chunk.  Returns {name: float64[samples, ...]} of
+        the stacked samples, "step": the steps done at each sample, and "fluid".  The
+        operator is linear: sums of the samples over time are the binned time sums."""
+        steps, every = int(steps), int(every)
+        if steps < 0 or every < 1:
+            raise ValueError("steps >= 0 and every >= 1")
+        which = self._bin_which(which)
+        samples, at, done = [], [], 0
+        while done < steps:
+            n = min(every, steps - done)
+            self.run_steps(n)
+            done += n
+            samples.append(self.binned(*bins, which=which))
+            at.append(done)
+        shape = self._bin_shape(tuple(int(b) for b in bins))
+        out = {n: (np.stack([s[n] for s in samples]) if samples else np.zeros((0,) + shape)) for n in which}
+        out["step"] = np.asarray(at, np.int64)
+        out["fluid"] = self.bin_fluid_cells(*bins)
+        return out
+
+
+class Engine(_WallForces, _Averages, _Gradients, _Stress, _Binned):
     """One lbm_handle: the HIP counterpart of the reference's poplar::Engine."""
 
     _FORCE_PREFIX = "lbm_"
     _AVG_FIELDS = AVG_FIELDS
     _GRAD_FIELDS = GRAD_FIELDS
     _STRESS_FIELDS = STRESS_FIELDS
+    _BIN_FIELDS = BIN_FIELDS
 
     def strain_rate_local(self, which=None):
         """[{name: float32[h][w]}] per local rect (local_rects() order; lbm_store_stress_local)."""
@@ -860,13 +974,14 @@ class Engine(_WallForces, _Averages, _Gradients, _Stress):
             pass
 
 
-class Engine3D(_WallForces, _Averages, _Gradients, _Stress):
+class Engine3D(_WallForces, _Averages, _Gradients, _Stress, _Binned):
     """One lbm3d_handle: the D3Q19 extension engine (include/lbm3d_hip.h)."""
 
     _FORCE_PREFIX = "lbm3d_"
     _AVG_FIELDS = AVG_FIELDS3D
     _GRAD_FIELDS = GRAD_FIELDS3D
     _STRESS_FIELDS = STRESS_FIELDS3D
+    _BIN_FIELDS = BIN_FIELDS3D
 
     def strain_rate_box(self, x0: int, y0: int, z0: int, nx: int, ny: int, nz: int, which=None):
         """{name: float32[nz][ny][nx]} of the cells [x0, x0+nx) x [y0, y0+ny) x [z0, z0+nz)
