@@ -18,15 +18,14 @@
 #include "lbm3d_engine.hpp"
 #include "lbm_binned.hpp"
 #include "lbm_binned_hip.h"
+#include "lbm_quad.hpp"
 
 namespace lbm {
 namespace binned {
 
-struct Bin3Args {
-    const float *o;        // lattice origin: plane z = 0 of the slab
-    const uint8_t *obst;   // uint8[nzs][ny][nx]
-    long long PL, KS;
-    int px, nx, ny;
+// the view of the whole slab; the kernel reads o, obst, PL, KS, px, nx and ny of it (the box, quad, sp and
+// obst_pressure ride along unused)
+struct Bin3Args : Box3View {
     Axis x;
     ChunkAxis z;
     int nwx, nslots;       // waves along x; partial slots of a (chunk, row)
@@ -52,8 +51,7 @@ __global__ __launch_bounds__(BN_BLOCK) void binned_sums3d(Bin3Args a) {
         for (int z = z0; z < z1; ++z) {
             const float *src = a.o + (long long)z * a.PL + (long long)y * a.px + x;
             float c[19];
-#pragma unroll
-            for (int k = 0; k < 19; ++k) c[k] = src[k * a.KS];
+            load_cell<19>(src, a.KS, 0, c);
             add_cell3(c, a.obst[((long long)z * a.ny + y) * a.nx + x] != 0, s[0]);
         }
     }
@@ -92,8 +90,7 @@ void lbm3d_handle::store_binned(int bw, int bh, int bd, double *const *out) {
     using namespace lbm::binned;
     if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to take binned sums of");
     check_bins(p, bw, bh, bd);
-    int want = 0;
-    for (int i = 0; out && i < LBM3D_BIN_FIELDS; ++i) want += out[i] ? 1 : 0;
+    const int want = count_wanted(out, LBM3D_BIN_FIELDS);
     if (want == 0) return;
     const int nbx = LBM_BIN_COUNT(p.nx, bw), nby = LBM_BIN_COUNT(p.ny, bh), nbz = LBM_BIN_COUNT(p.nz, bd);
     const size_t layer = (size_t)nbx * nby;
@@ -102,15 +99,7 @@ void lbm3d_handle::store_binned(int bw, int bh, int bd, double *const *out) {
     sync_all();
     for (auto &s : slabs) {
         HIP_CHECK(hipSetDevice(s.dev));
-        const Fields3Args f = fields_args(s, 0, 0, 0, p.nx, p.ny, s.nzs);
-        Bin3Args a{};
-        a.o = f.o;
-        a.obst = f.obst;
-        a.PL = f.PL;
-        a.KS = f.KS;
-        a.px = f.px;
-        a.nx = p.nx;
-        a.ny = p.ny;
+        Bin3Args a{box_view(s, 0, 0, 0, p.nx, p.ny, s.nzs)};
         a.x = make_axis(0, p.nx, bw);
         a.z = make_chunk_axis(s.z0, s.nzs, bd);
         a.nwx = (p.nx + BN3_WAVE_COLS - 1) / BN3_WAVE_COLS;

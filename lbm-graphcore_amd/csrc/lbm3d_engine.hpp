@@ -11,6 +11,8 @@
 //   lbm3d_stress.hip   strain rate and wall shear from the non-equilibrium moments (kernel + host side);
 //   lbm3d_binned.hip   sums over box-shaped bins of the current lattice (kernel + host side);
 //   lbm3d_abi.hip      the extern "C" functions and the RCCL posting order.
+// The diagnostics units (fields to binned) share their host paths through
+// lbm_diag_host.hpp and their cell reads and block fold through lbm_quad.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -23,7 +25,7 @@
 
 #include "lbm3d_fields.hpp"
 #include "lbm3d_fields_hip.h"
-#include "lbm_common.hpp"
+#include "lbm_diag_host.hpp"
 #include "lbm_forces.hpp"
 #include "lbm_forces_hip.h"
 
@@ -224,7 +226,13 @@ struct lbm3d_handle {
     void store(float *aos, float *av, int n_av);
     void destroy();
     // lbm3d_fields.hip
-    lbm::Fields3Args fields_args(const lbm::Slab &s, int x0, int y0, int z0, int bx, int by, int bz) const;
+    lbm::Box3View box_view(const lbm::Slab &s, int x0, int y0, int z0, int bx, int by, int bz) const;
+    void check_box(const lbm3d_box &b) const;
+    bool slab_planes(const lbm::Slab &s, const lbm3d_box &b, int &zlo, int &zhi) const;
+    // where the box's planes from global plane zlo on lie in a packed host array float[b.nz][b.ny][b.nx]
+    static lbm::HostSpan box_span(const lbm3d_box &b, int zlo) {
+        return lbm::HostSpan{(size_t)(zlo - b.z0) * b.ny * b.nx, (size_t)b.nx};
+    }
     void store_fields_box(const lbm3d_box &b, float *const (&host)[5]);
     void field_stats(double *mass, float *max_speed);
     // lbm3d_forces.hip

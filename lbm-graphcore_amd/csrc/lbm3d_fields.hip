@@ -8,10 +8,9 @@
 // 20 B written per cell, no reuse, no LDS staging.  A box at least 4 cells
 // wide whose x origin is a multiple of 4 (every full-row box: the whole
 // domain, z- and y-normal planes) gives one lane four consecutive cells of a
-// row (Fields3Args::quad): lattice rows start 16-B aligned (px is a multiple
-// of 16 floats, KS and PL multiples of 4), so that is nineteen 16-B loads and
-// up to five 16-B stores into staging rows padded to 4 floats; the last
-// bx % 4 cells of a row take a scalar path.  Other boxes take one cell per
+// row (Box3View::quad) by the access path of lbm_quad.hpp: nineteen 16-B loads
+// and up to five 16-B stores into staging rows padded to 4 floats; the last
+// bx % 4 cells of a row go one at a time.  Other boxes take one cell per
 // lane and stage unpadded rows.  A block is 64 lanes along x by 4 rows;
 // blockIdx.y / .z walk rows and planes, so no index is ever divided and the
 // float offsets are formed in 64 bits (512^3 x 19 floats exceeds 2^31).
@@ -27,6 +26,7 @@
 
 #include "lbm3d_cell_macro.hpp"
 #include "lbm3d_engine.hpp"
+#include "lbm_quad.hpp"
 
 namespace lbm {
 
@@ -69,21 +69,13 @@ __global__ __launch_bounds__(F3X *F3Y) void macroscopic_fields3d(Fields3Args a) 
                 const long long so = ((long long)z * a.by + y) * a.sp + x;
                 if (quad && x + 4 <= a.bx) {
                     float4 v[F3Q];
-#pragma unroll
-                    for (int k = 0; k < F3Q; ++k) v[k] = *reinterpret_cast<const float4 *>(src + k * a.KS);
-                    unsigned bits;
-                    if (obst_word)
-                        bits = *reinterpret_cast<const unsigned *>(ob);
-                    else
-                        bits = (unsigned)ob[0] | ((unsigned)ob[1] << 8) | ((unsigned)ob[2] << 16) |
-                               ((unsigned)ob[3] << 24);
+                    load_quad<F3Q>(src, a.KS, v);
+                    const unsigned bits = quad_map_bytes(ob, obst_word);
                     Cell3Macro m[4];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         float s[F3Q];
-#pragma unroll
-                        for (int k = 0; k < F3Q; ++k)
-                            s[k] = i == 0 ? v[k].x : i == 1 ? v[k].y : i == 2 ? v[k].z : v[k].w;
+                        quad_cell<F3Q>(v, i, s);
                         const bool blocked = ((bits >> (8 * i)) & 0xffu) != 0;
                         float rho;
                         m[i] = cell3_dispatch(s, blocked, a.obst_pressure, want_v, want_u, rho);
@@ -103,8 +95,7 @@ __global__ __launch_bounds__(F3X *F3Y) void macroscopic_fields3d(Fields3Args a) 
                     // one cell per lane, or the ragged tail of a row: its last bx % 4 cells, one at a time
                     for (int i = 0; i < cpl && x + i < a.bx; ++i) {
                         float s[F3Q];
-#pragma unroll
-                        for (int k = 0; k < F3Q; ++k) s[k] = src[k * a.KS + i];
+                        load_cell<F3Q>(src, a.KS, i, s);
                         const bool blocked = ob[i] != 0;
                         float rho;
                         const Cell3Macro m = cell3_dispatch(s, blocked, a.obst_pressure, want_v, want_u, rho);
@@ -123,30 +114,11 @@ __global__ __launch_bounds__(F3X *F3Y) void macroscopic_fields3d(Fields3Args a) 
         }
     }
     if (STATS) {
-        // lanes of a wave by shuffle, the block's four waves through LDS: fixed order
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mass += __shfl_down(mass, off, 64);
-            umax = fmaxf(umax, __shfl_down(umax, off, 64));
-        }
-        __shared__ double wmass[F3Y];
-        __shared__ float wmax[F3Y];
-        if (tx == 0) {
-            wmass[ty] = mass;
-            wmax[ty] = umax;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double ms = wmass[0];
-            float mx = wmax[0];
-            for (int i = 1; i < F3Y; ++i) {
-                ms += wmass[i];
-                mx = fmaxf(mx, wmax[i]);
-            }
-            const long long b = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-            a.mass_part[b] = ms;
-            a.umax_part[b] = mx;
-        }
+        double s[1] = {mass};
+        float m[1] = {umax};
+        const long long b = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        // a row of the block is a wave
+        fold_block<F3Y>(s, m, b, (long long)gridDim.x * gridDim.y * gridDim.z, a.mass_part, a.umax_part);
     }
 }
 
@@ -184,11 +156,23 @@ hipError_t launch_macroscopic_fields3d(const Fields3Args &a, bool stats, hipStre
 using namespace lbm;
 
 // the cells [x0, x0+bx) x [y0, y0+by) x [z0, z0+bz) of slab s (z0 slab-local)
-Fields3Args lbm3d_handle::fields_args(const Slab &s, int x0, int y0, int z0, int bx, int by, int bz) const {
+Box3View lbm3d_handle::box_view(const Slab &s, int x0, int y0, int z0, int bx, int by, int bz) const {
     const int quad = (x0 % 4 == 0 && bx >= 4) ? 1 : 0;  // every full-row box of a domain >= 4 cells wide
-    // o, obst, strides, plane extents, box, quad, sp, obst_pressure; the output pointers stay null
-    return Fields3Args{s.o[s.cur], s.obst, PL, KS, px, p.nx, p.ny, x0, y0, z0, bx, by, bz,
-                       quad, quad ? (bx + 3) / 4 * 4 : bx, p.density * (1.f / 3.f)};
+    return Box3View{s.o[s.cur], s.obst, PL, KS, px, p.nx, p.ny, x0, y0, z0, bx, by, bz,
+                    quad, quad ? (bx + 3) / 4 * 4 : bx, p.density * (1.f / 3.f)};
+}
+
+void lbm3d_handle::check_box(const lbm3d_box &b) const {
+    if (b.nx <= 0 || b.ny <= 0 || b.nz <= 0 || b.x0 < 0 || b.y0 < 0 || b.z0 < 0 ||
+        (long long)b.x0 + b.nx > p.nx || (long long)b.y0 + b.ny > p.ny || (long long)b.z0 + b.nz > p.nz)
+        throw lbm_failure(LBM_E_INVALID, "box must be non-empty and inside the domain");
+}
+
+// the planes [zlo, zhi) (global) of box b that lie in slab s; false: none
+bool lbm3d_handle::slab_planes(const Slab &s, const lbm3d_box &b, int &zlo, int &zhi) const {
+    zlo = std::max(b.z0, s.z0);
+    zhi = std::min(b.z0 + b.nz, s.z0 + s.nzs);
+    return zlo < zhi;
 }
 
 // u_x, u_y, u_z, |u|, pressure of the box's cells into the packed planar
@@ -198,65 +182,45 @@ Fields3Args lbm3d_handle::fields_args(const Slab &s, int x0, int y0, int z0, int
 // floats on the 16-B path) and copied to its planes of the host arrays.
 void lbm3d_handle::store_fields_box(const lbm3d_box &b, float *const (&host)[5]) {
     if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to derive fields from");
-    if (b.nx <= 0 || b.ny <= 0 || b.nz <= 0 || b.x0 < 0 || b.y0 < 0 || b.z0 < 0 ||
-        (long long)b.x0 + b.nx > p.nx || (long long)b.y0 + b.ny > p.ny || (long long)b.z0 + b.nz > p.nz)
-        throw lbm_failure(LBM_E_INVALID, "box must be non-empty and inside the domain");
-    int want = 0;
-    for (float *f : host) want += f ? 1 : 0;
+    check_box(b);
+    const int want = count_wanted(host, 5);
     if (want == 0) return;
     sync_all();
     for (auto &s : slabs) {
-        const int zlo = std::max(b.z0, s.z0), zhi = std::min(b.z0 + b.nz, s.z0 + s.nzs);
-        if (zlo >= zhi) continue;
+        int zlo, zhi;
+        if (!slab_planes(s, b, zlo, zhi)) continue;
         HIP_CHECK(hipSetDevice(s.dev));
-        Fields3Args a = fields_args(s, b.x0, b.y0, zlo - s.z0, b.nx, b.ny, zhi - zlo);
-        const size_t rows = (size_t)a.by * a.bz, field_floats = rows * a.sp;
-        const DeviceStage stage(sizeof(float) * field_floats * want);
+        Fields3Args a{box_view(s, b.x0, b.y0, zlo - s.z0, b.nx, b.ny, zhi - zlo)};
+        const size_t rows = (size_t)a.by * a.bz;
+        const PlanarStage stage(want, rows * a.sp);
         float **dev[5] = {&a.ux, &a.uy, &a.uz, &a.speed, &a.pressure};
         for (int i = 0, n = 0; i < 5; ++i)
-            if (host[i]) *dev[i] = stage.as<float>() + field_floats * n++;
+            if (host[i]) *dev[i] = stage.field(n++);
         HIP_CHECK(launch_macroscopic_fields3d(a, false, s.s_comp));
         HIP_CHECK(hipStreamSynchronize(s.s_comp));
-        const size_t off = (size_t)(zlo - b.z0) * b.ny * b.nx;
-        for (int i = 0; i < 5; ++i) {
-            if (!host[i]) continue;
-            if (a.sp == b.nx)  // no row padding: one contiguous copy
-                HIP_CHECK(hipMemcpy(host[i] + off, *dev[i], sizeof(float) * field_floats, hipMemcpyDeviceToHost));
-            else
-                HIP_CHECK(hipMemcpy2D(host[i] + off, sizeof(float) * (size_t)b.nx, *dev[i], sizeof(float) * (size_t)a.sp,
-                                      sizeof(float) * (size_t)b.nx, rows, hipMemcpyDeviceToHost));
-        }
+        stage.copy_out(host, 5, box_span(b, zlo), (size_t)a.sp, (size_t)b.nx, rows);
     }
 }
 
 // Total mass (fp64 sum of every local cell's fp32 density) and the largest
-// |u| over the local fluid cells.  The kernel leaves per-block partials;
-// they are folded here in block order, slab after slab, so the same
-// lattice always gives the same bits.
+// |u| over the local fluid cells, from the kernel's per-block partials
+// (BlockPartials, lbm_diag_host.hpp), slab after slab.
 void lbm3d_handle::field_stats(double *mass, float *max_speed) {
     if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to take statistics of");
     if (!mass && !max_speed) return;
     sync_all();
-    double total = 0.0;
-    float umax = 0.f;
+    double total[1] = {0.0};
+    float umax[1] = {0.f};
     for (auto &s : slabs) {
         HIP_CHECK(hipSetDevice(s.dev));
-        Fields3Args a = fields_args(s, 0, 0, 0, p.nx, p.ny, s.nzs);
-        const size_t nb = (size_t)fields3d_blocks(a);
-        const DeviceStage part((sizeof(double) + sizeof(float)) * nb);  // [nb doubles | nb floats]
-        std::vector<double> hm(nb);
-        std::vector<float> hu(nb);
-        a.mass_part = part.as<double>();
-        a.umax_part = reinterpret_cast<float *>(a.mass_part + nb);
+        Fields3Args a{box_view(s, 0, 0, 0, p.nx, p.ny, s.nzs)};
+        const BlockPartials<1, 1> part((size_t)fields3d_blocks(a));
+        a.mass_part = part.sums();
+        a.umax_part = part.maxima();
         HIP_CHECK(launch_macroscopic_fields3d(a, true, s.s_comp));
         HIP_CHECK(hipStreamSynchronize(s.s_comp));
-        HIP_CHECK(hipMemcpy(hm.data(), a.mass_part, sizeof(double) * nb, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(hu.data(), a.umax_part, sizeof(float) * nb, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < nb; ++i) {
-            total += hm[i];
-            umax = std::max(umax, hu[i]);
-        }
+        part.fold(total, umax);
     }
-    if (mass) *mass = total;
-    if (max_speed) *max_speed = umax;
+    if (mass) *mass = total[0];
+    if (max_speed) *max_speed = umax[0];
 }

@@ -6,23 +6,13 @@
 
 #include <cstdint>
 
+#include "lbm_views.hpp"
+
 namespace lbm {
 
-// Fields of the bx x by x bz cells at (x0, y0, z0) of one slab's current
-// lattice into the planar staging arrays float[bz][by][sp]; a null array is
-// neither computed nor stored.  quad (x0 % 4 == 0 and bx >= 4 required): four
-// cells per lane with 16-B accesses, sp = roundup(bx, 4); else one cell per
-// lane, sp = bx.
-struct Fields3Args {
-    const float *o;        // lattice origin: plane z = 0 of the slab
-    const uint8_t *obst;   // uint8[nzs][ny][nx] of the slab
-    long long PL, KS;      // plane stride, speed stride (floats)
-    int px, nx, ny;        // row pitch (floats) and extents of a lattice plane
-    int x0, y0, z0;        // box origin (z0 slab-local)
-    int bx, by, bz;        // box extents (> 0, inside the slab)
-    int quad;              // access path, see above
-    int sp;                // staging row pitch (floats)
-    float obst_pressure;   // pressure reported for an obstacle cell: density * (1/3)
+// Fields of the view's box (lbm_views.hpp) into the planar staging arrays
+// float[bz][by][sp]; a null array is neither computed nor stored.
+struct Fields3Args : Box3View {
     float *ux, *uy, *uz, *speed, *pressure;
     double *mass_part;     // stats launch: per-block fp64 sums of the cells' densities
     float *umax_part;      // stats launch: per-block max |u| over fluid cells

@@ -123,8 +123,7 @@ void lbm3d_handle::wall_force(double *fx, double *fy, double *fz, int64_t *links
 // scattered into zeroed staging arrays of the slab, copied to its planes
 void lbm3d_handle::store_wall_force(float *const (&host)[3]) {
     if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to take wall forces of");
-    int want = 0;
-    for (float *f : host) want += f ? 1 : 0;
+    const int want = count_wanted(host, 3);
     if (want == 0) return;
     sync_all();
     walls_build();
@@ -133,18 +132,15 @@ void lbm3d_handle::store_wall_force(float *const (&host)[3]) {
         HIP_CHECK(hipSetDevice(s.dev));
         const forces::WallList &wl = walls[k];
         forces::WallArgs a = wl.args(s.o[s.cur], KS);
-        const size_t field_floats = (size_t)s.nzs * p.ny * p.nx;
-        const DeviceStage stage(sizeof(float) * field_floats * want);
-        HIP_CHECK(hipMemsetAsync(stage.get(), 0, sizeof(float) * field_floats * want, s.s_comp));
+        const size_t rows = (size_t)s.nzs * p.ny;
+        const PlanarStage stage(want, rows * p.nx);
+        HIP_CHECK(hipMemsetAsync(stage.get(), 0, stage.bytes(), s.s_comp));
         float **dev[3] = {&a.mx, &a.my, &a.mz};
         for (int i = 0, n = 0; i < 3; ++i)
-            if (host[i]) *dev[i] = stage.as<float>() + field_floats * n++;
+            if (host[i]) *dev[i] = stage.field(n++);
         HIP_CHECK(wl.launch(forces::WALL_MAP, a, s.s_comp));
         HIP_CHECK(hipStreamSynchronize(s.s_comp));
-        for (int i = 0; i < 3; ++i)
-            if (host[i])
-                HIP_CHECK(hipMemcpy(host[i] + (size_t)s.z0 * p.ny * p.nx, *dev[i], sizeof(float) * field_floats,
-                                    hipMemcpyDeviceToHost));
+        stage.copy_out(host, 3, HostSpan{(size_t)s.z0 * p.ny * p.nx, (size_t)p.nx}, (size_t)p.nx, (size_t)p.nx, rows);
     }
 }
 

@@ -10,7 +10,7 @@
 //
 // velocity_gradients3d: a block owns a tile of 64 x 16 cells of a plane and
 // walks a segment of 32 planes in z.  A thread takes four consecutive cells
-// (nineteen 16-B loads per plane, as macroscopic_fields3d) and keeps the
+// (nineteen 16-B loads per plane, lbm_quad.hpp) and keeps the
 // velocities of three planes in registers (36 VGPRs), so each population of
 // the tile is read once per plane; the in-plane neighbours go through LDS:
 // the centre plane's velocities as aligned float4 rows, plus the 160 cells
@@ -27,6 +27,7 @@
 #include "lbm3d_engine.hpp"
 #include "lbm_gradients.hpp"
 #include "lbm_gradients_hip.h"
+#include "lbm_quad.hpp"
 
 namespace lbm {
 namespace grad {
@@ -41,8 +42,7 @@ __device__ __forceinline__ void cell3_velocity(const Grad3Args &a, int xg, int y
                                                bool &blocked) {
     const float *src = a.o + (long long)lz * a.PL + (long long)yg * a.px + xg;
     float s[G3Q];
-#pragma unroll
-    for (int k = 0; k < G3Q; ++k) s[k] = src[k * a.KS];
+    load_cell<G3Q>(src, a.KS, 0, s);
     blocked = a.obst[((long long)lz * a.ny + yg) * a.nx + xg] != 0;
     float rho;
     const Cell3Macro m = cell3_macro<true, false>(s, blocked, a.obst_pressure, rho);
@@ -54,8 +54,8 @@ __device__ __forceinline__ void cell3_velocity(const Grad3Args &a, int xg, int y
 // The velocities of the thread's four cells (box-local x .. x + 3, row y) of
 // slab plane lz (-1 <= lz <= nzs): every cell the tile's stencils can touch
 // (x + i <= bx, y <= by, wrapped into the plane), +0 elsewhere.
-__device__ __forceinline__ void load_quad(const Grad3Args &a, int x, int y, int lz, float (&u)[3][4],
-                                          unsigned &blocked) {
+__device__ __forceinline__ void quad_velocities(const Grad3Args &a, int x, int y, int lz, float (&u)[3][4],
+                                                unsigned &blocked) {
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
@@ -82,18 +82,12 @@ __device__ __forceinline__ void load_quad(const Grad3Args &a, int x, int y, int 
         const float *src = a.o + (long long)lz * a.PL + (long long)yg * a.px + xg;
         const uint8_t *ob = a.obst + ((long long)lz * a.ny + yg) * a.nx + xg;
         float4 v[G3Q];
-#pragma unroll
-        for (int k = 0; k < G3Q; ++k) v[k] = *reinterpret_cast<const float4 *>(src + k * a.KS);
-        unsigned bits;
-        if ((a.nx & 3) == 0)
-            bits = *reinterpret_cast<const unsigned *>(ob);
-        else
-            bits = (unsigned)ob[0] | ((unsigned)ob[1] << 8) | ((unsigned)ob[2] << 16) | ((unsigned)ob[3] << 24);
+        load_quad<G3Q>(src, a.KS, v);
+        const unsigned bits = quad_map_bytes(ob, (a.nx & 3) == 0);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             float s[G3Q];
-#pragma unroll
-            for (int k = 0; k < G3Q; ++k) s[k] = i == 0 ? v[k].x : i == 1 ? v[k].y : i == 2 ? v[k].z : v[k].w;
+            quad_cell<G3Q>(v, i, s);
             const bool b = ((bits >> (8 * i)) & 0xffu) != 0;
             if (b) blocked |= 1u << i;
             float rho;
@@ -122,7 +116,7 @@ __device__ __forceinline__ void load_quad(const Grad3Args &a, int x, int y, int 
 }  // namespace
 
 // STATS: no field is stored; block b (x fastest, then y, then z) writes its
-// partial sums and maxima over the fluid cells it owns (fold_stats).
+// partial sums and maxima over the fluid cells it owns (fold_block, lbm_quad.hpp).
 template <bool STATS>
 __global__ __launch_bounds__(G3T) void velocity_gradients3d(Grad3Args a) {
     // centre plane: rows -1 .. G3Y of the tile (index + 1), then the columns -1 and G3W beside it
@@ -154,11 +148,11 @@ __global__ __launch_bounds__(G3T) void velocity_gradients3d(Grad3Args a) {
     float mw = 0.f, md = 0.f;
     float p[3][4], c[3][4], n[3][4];
     unsigned pb, cb, nb;
-    load_quad(a, x, y, a.z0 + zs - 1, p, pb);
-    load_quad(a, x, y, a.z0 + zs, c, cb);
+    quad_velocities(a, x, y, a.z0 + zs - 1, p, pb);
+    quad_velocities(a, x, y, a.z0 + zs, c, cb);
     for (int z = zs; z < ze; ++z) {
         const int lz = a.z0 + z;
-        load_quad(a, x, y, lz + 1, n, nb);
+        quad_velocities(a, x, y, lz + 1, n, nb);
         float hu[3] = {0.f, 0.f, 0.f};
         if (halo) {
             bool b;
@@ -239,8 +233,10 @@ __global__ __launch_bounds__(G3T) void velocity_gradients3d(Grad3Args a) {
     }
     (void)pb;
     if (STATS) {
+        double s[2] = {sw2, ss2};
+        float m[2] = {mw, md};
         const long long b = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        fold_stats<G3T / 64>(sw2, ss2, mw, md, b, (long long)gridDim.x * gridDim.y * gridDim.z, a.sum_part, a.max_part);
+        fold_block<G3T / 64>(s, m, b, (long long)gridDim.x * gridDim.y * gridDim.z, a.sum_part, a.max_part);
     }
 }
 
@@ -284,8 +280,7 @@ int lbm3d_handle::grad_prepare() {
         throw lbm_failure(LBM_E_INVALID,
                           "velocity gradients are not built for RCCL handles of world size > 1: the neighbours' "
                           "face velocities live in other processes");
-    const Fields3Args probe = fields_args(slabs[0], 0, 0, 0, p.nx, p.ny, 1);
-    const int hp = probe.sp;
+    const int hp = box_view(slabs[0], 0, 0, 0, p.nx, p.ny, 1).sp;
     const size_t plane = (size_t)3 * p.ny * hp;
     if (grad_faces.empty()) {
         grad_faces.assign(slabs.size(), nullptr);
@@ -298,7 +293,7 @@ int lbm3d_handle::grad_prepare() {
         const Slab &s = slabs[k];
         HIP_CHECK(hipSetDevice(s.dev));
         for (int top = 0; top < 2; ++top) {
-            Fields3Args a = fields_args(s, 0, 0, top == 0 ? s.nzs - 1 : 0, p.nx, p.ny, 1);
+            Fields3Args a{box_view(s, 0, 0, top == 0 ? s.nzs - 1 : 0, p.nx, p.ny, 1)};
             float *buf = grad_faces[k] + (size_t)top * plane;
             a.ux = buf;
             a.uy = buf + (size_t)p.ny * hp;
@@ -343,24 +338,11 @@ void lbm3d_handle::grad_release() {
 Grad3Args lbm3d_handle::grad_args(size_t k, int hp, int x0, int y0, int z0, int bx, int by, int bz) const {
     const Slab &s = slabs[k];
     const size_t plane = (size_t)3 * p.ny * hp;
-    Grad3Args a{};
-    a.o = s.o[s.cur];
-    a.obst = s.obst;
-    a.PL = PL;
-    a.KS = KS;
-    a.px = px;
-    a.nx = p.nx;
-    a.ny = p.ny;
+    Grad3Args a{box_view(s, x0, y0, z0, bx, by, bz)};
     a.nzs = s.nzs;
-    a.x0 = x0;
-    a.y0 = y0;
-    a.z0 = z0;
-    a.bx = bx;
-    a.by = by;
-    a.bz = bz;
+    // a thread owns four cells of a row whatever the box: aligned boxes narrower than 4 too, rows always padded
     a.quad = x0 % 4 == 0 ? 1 : 0;
     a.sp = (bx + 3) / 4 * 4;
-    a.obst_pressure = p.density * (1.f / 3.f);
     a.above = grad_faces[k] + 2 * plane;
     a.below = grad_faces[k] + 3 * plane;
     a.hp = hp;
@@ -372,72 +354,50 @@ Grad3Args lbm3d_handle::grad_args(size_t k, int hp, int x0, int y0, int z0, int 
 // staged), slab by slab as store_fields_box.
 void lbm3d_handle::store_gradients_box(const lbm3d_box &b, float *const *host) {
     if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to derive gradients from");
-    if (b.nx <= 0 || b.ny <= 0 || b.nz <= 0 || b.x0 < 0 || b.y0 < 0 || b.z0 < 0 ||
-        (long long)b.x0 + b.nx > p.nx || (long long)b.y0 + b.ny > p.ny || (long long)b.z0 + b.nz > p.nz)
-        throw lbm_failure(LBM_E_INVALID, "box must be non-empty and inside the domain");
-    int want = 0;
-    for (int i = 0; host && i < LBM3D_GRAD_FIELDS; ++i) want += host[i] ? 1 : 0;
+    check_box(b);
+    const int want = count_wanted(host, LBM3D_GRAD_FIELDS);
     if (want == 0) return;
     sync_all();
     const int hp = grad_prepare();
     for (size_t k = 0; k < slabs.size(); ++k) {
         const Slab &s = slabs[k];
-        const int zlo = std::max(b.z0, s.z0), zhi = std::min(b.z0 + b.nz, s.z0 + s.nzs);
-        if (zlo >= zhi) continue;
+        int zlo, zhi;
+        if (!slab_planes(s, b, zlo, zhi)) continue;
         HIP_CHECK(hipSetDevice(s.dev));
         Grad3Args a = grad_args(k, hp, b.x0, b.y0, zlo - s.z0, b.nx, b.ny, zhi - zlo);
-        const size_t rows = (size_t)a.by * a.bz, field_floats = rows * a.sp;
-        const DeviceStage stage(sizeof(float) * field_floats * want);
+        const size_t rows = (size_t)a.by * a.bz;
+        const PlanarStage stage(want, rows * a.sp);
         for (int i = 0, n = 0; i < LBM3D_GRAD_FIELDS; ++i)
-            if (host[i]) a.out[i] = stage.as<float>() + field_floats * n++;
+            if (host[i]) a.out[i] = stage.field(n++);
         HIP_CHECK(grad::launch_velocity_gradients3d(a, false, s.s_comp));
         HIP_CHECK(hipStreamSynchronize(s.s_comp));
-        const size_t off = (size_t)(zlo - b.z0) * b.ny * b.nx;
-        for (int i = 0; i < LBM3D_GRAD_FIELDS; ++i) {
-            if (!host[i]) continue;
-            if (a.sp == b.nx)  // no row padding: one contiguous copy
-                HIP_CHECK(hipMemcpy(host[i] + off, a.out[i], sizeof(float) * field_floats, hipMemcpyDeviceToHost));
-            else
-                HIP_CHECK(hipMemcpy2D(host[i] + off, sizeof(float) * (size_t)b.nx, a.out[i],
-                                      sizeof(float) * (size_t)a.sp, sizeof(float) * (size_t)b.nx, rows,
-                                      hipMemcpyDeviceToHost));
-        }
+        stage.copy_out(host, LBM3D_GRAD_FIELDS, box_span(b, zlo), (size_t)a.sp, (size_t)b.nx, rows);
     }
 }
 
 // Sums of |vorticity|^2 and S:S (fp64) and the largest |vorticity| and
-// |divergence| over the local fluid cells; per-block partials folded here in
-// block order, slab after slab.
+// |divergence| over the local fluid cells, from the kernel's per-block
+// partials (BlockPartials, lbm_diag_host.hpp), slab after slab.
 void lbm3d_handle::gradient_stats(double *sum_w2, double *sum_s2, float *max_w, float *max_div) {
     if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to take statistics of");
     if (!sum_w2 && !sum_s2 && !max_w && !max_div) return;
     sync_all();
     const int hp = grad_prepare();
-    double tw = 0.0, ts = 0.0;
-    float mw = 0.f, md = 0.f;
+    double sum[2] = {0.0, 0.0};  // w2, s2
+    float max[2] = {0.f, 0.f};   // |vorticity|, |divergence|
     for (size_t k = 0; k < slabs.size(); ++k) {
         const Slab &s = slabs[k];
         HIP_CHECK(hipSetDevice(s.dev));
         Grad3Args a = grad_args(k, hp, 0, 0, 0, p.nx, p.ny, s.nzs);
-        const size_t nb = (size_t)grad::gradients3d_blocks(a);
-        const DeviceStage part((sizeof(double) + sizeof(float)) * 2 * nb);  // [2 nb doubles | 2 nb floats]
-        a.sum_part = part.as<double>();
-        a.max_part = reinterpret_cast<float *>(a.sum_part + 2 * nb);
+        const BlockPartials<2, 2> part((size_t)grad::gradients3d_blocks(a));
+        a.sum_part = part.sums();
+        a.max_part = part.maxima();
         HIP_CHECK(grad::launch_velocity_gradients3d(a, true, s.s_comp));
         HIP_CHECK(hipStreamSynchronize(s.s_comp));
-        std::vector<double> hs(2 * nb);
-        std::vector<float> hm(2 * nb);
-        HIP_CHECK(hipMemcpy(hs.data(), a.sum_part, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(hm.data(), a.max_part, sizeof(float) * 2 * nb, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < nb; ++i) {
-            tw += hs[i];
-            ts += hs[nb + i];
-            mw = std::max(mw, hm[i]);
-            md = std::max(md, hm[nb + i]);
-        }
+        part.fold(sum, max);
     }
-    if (sum_w2) *sum_w2 = tw;
-    if (sum_s2) *sum_s2 = ts;
-    if (max_w) *max_w = mw;
-    if (max_div) *max_div = md;
+    if (sum_w2) *sum_w2 = sum[0];
+    if (sum_s2) *sum_s2 = sum[1];
+    if (max_w) *max_w = max[0];
+    if (max_div) *max_div = max[1];
 }

@@ -6,10 +6,9 @@
 // Cell-local, so every transport and world size works.  One memory-bound pass
 // over the 19 populations of the current lattice: 77 B read per cell, 4 B
 // written per requested field, no LDS but the statistics' fold.  The access
-// paths are macroscopic_fields3d's: a box at least 4 cells wide whose x origin
-// is a multiple of 4 gives a lane four consecutive cells of a row (nineteen
-// 16-B loads, a float4 store per field into staging rows padded to 4 floats,
-// the last bx % 4 cells one at a time); other boxes take one cell per lane.  A
+// paths are macroscopic_fields3d's (Box3View::quad, lbm_quad.hpp): four
+// consecutive cells of a row per lane with a float4 store per field into
+// staging rows padded to 4 floats, or one cell per lane.  A
 // block is 64 lanes along x by S3Y rows and walks S3Z consecutive planes;
 // offsets are formed in 64 bits.
 //
@@ -22,7 +21,7 @@
 #include <vector>
 
 #include "lbm3d_engine.hpp"
-#include "lbm_gradients.hpp"
+#include "lbm_quad.hpp"
 #include "lbm_stress.hpp"
 #include "lbm_stress_hip.h"
 
@@ -54,7 +53,7 @@ __device__ __forceinline__ Strain3 cell(const float (&c)[Q3], unsigned cls, floa
 }  // namespace
 
 // STATS: no field is stored and a.obst is the class map; block b (x fastest,
-// then y, then z) writes its partial sums and maxima (grad::fold_stats).
+// then y, then z) writes its partial sums and maxima (fold_block, lbm_quad.hpp).
 template <bool STATS>
 __global__ __launch_bounds__(S3X *S3Y) void neq_strain3d(Stress3Args a) {
     const bool quad = a.quad != 0;
@@ -73,21 +72,13 @@ __global__ __launch_bounds__(S3X *S3Y) void neq_strain3d(Stress3Args a) {
                 const long long so = ((long long)z * a.by + y) * a.sp + x;
                 if (quad && x + 4 <= a.bx) {
                     float4 v[Q3];
-#pragma unroll
-                    for (int k = 0; k < Q3; ++k) v[k] = *reinterpret_cast<const float4 *>(src + k * a.KS);
-                    unsigned bits;
-                    if (obst_word)
-                        bits = *reinterpret_cast<const unsigned *>(ob);
-                    else
-                        bits = (unsigned)ob[0] | ((unsigned)ob[1] << 8) | ((unsigned)ob[2] << 16) |
-                               ((unsigned)ob[3] << 24);
+                    load_quad<Q3>(src, a.KS, v);
+                    const unsigned bits = quad_map_bytes(ob, obst_word);
                     Strain3 s[4];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         float c[Q3];
-#pragma unroll
-                        for (int k = 0; k < Q3; ++k)
-                            c[k] = i == 0 ? v[k].x : i == 1 ? v[k].y : i == 2 ? v[k].z : v[k].w;
+                        quad_cell<Q3>(v, i, c);
                         s[i] = cell<STATS>(c, (bits >> (8 * i)) & 0xffu, a.coef, acc);
                     }
                     if (!STATS) {
@@ -106,8 +97,7 @@ __global__ __launch_bounds__(S3X *S3Y) void neq_strain3d(Stress3Args a) {
                     // one cell per lane, or the ragged tail of a row: its last bx % 4 cells, one at a time
                     for (int i = 0; i < cpl && x + i < a.bx; ++i) {
                         float c[Q3];
-#pragma unroll
-                        for (int k = 0; k < Q3; ++k) c[k] = src[k * a.KS + i];
+                        load_cell<Q3>(src, a.KS, i, c);
                         const Strain3 s = cell<STATS>(c, ob[i], a.coef, acc);
                         if (!STATS) {
                             if (a.out[0]) a.out[0][so + i] = s.sxx;
@@ -124,9 +114,10 @@ __global__ __launch_bounds__(S3X *S3Y) void neq_strain3d(Stress3Args a) {
         }
     }
     if (STATS) {
+        double s[2] = {acc.sum_s2, acc.sum_wall};
+        float m[2] = {acc.max_s, acc.max_wall};
         const long long b = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        grad::fold_stats<S3Y>(acc.sum_s2, acc.sum_wall, acc.max_s, acc.max_wall, b,
-                              (long long)gridDim.x * gridDim.y * gridDim.z, a.sum_part, a.max_part);
+        fold_block<S3Y>(s, m, b, (long long)gridDim.x * gridDim.y * gridDim.z, a.sum_part, a.max_part);
     }
 }
 
@@ -177,29 +168,8 @@ using lbm::stress::Stress3Args;
 // the cells [x0, x0+bx) x [y0, y0+by) x [z0, z0+bz) of slab s (z0 slab-local); the output pointers stay
 // null.  Refuses omega = 1.
 Stress3Args lbm3d_handle::stress_args(const Slab &s, int x0, int y0, int z0, int bx, int by, int bz) const {
-    const float omo = 1.f - p.omega;
-    if (omo == 0.f)
-        throw lbm_failure(LBM_E_INVALID,
-                          "omega = 1: the post-collision lattice carries no non-equilibrium part to take the strain "
-                          "rate from");
-    const Fields3Args f = fields_args(s, x0, y0, z0, bx, by, bz);
-    Stress3Args a{};
-    a.o = f.o;
-    a.obst = f.obst;
-    a.PL = f.PL;
-    a.KS = f.KS;
-    a.px = f.px;
-    a.nx = f.nx;
-    a.ny = f.ny;
-    a.x0 = x0;
-    a.y0 = y0;
-    a.z0 = z0;
-    a.bx = bx;
-    a.by = by;
-    a.bz = bz;
-    a.quad = f.quad;
-    a.sp = f.sp;
-    a.coef = (-1.5f * p.omega) / omo;
+    Stress3Args a{box_view(s, x0, y0, z0, bx, by, bz)};
+    a.coef = neq_strain_coef(p.omega);
     return a;
 }
 
@@ -261,41 +231,29 @@ void lbm3d_handle::stress_release() {
 // staged), slab by slab as store_fields_box.
 void lbm3d_handle::store_stress_box(const lbm3d_box &b, float *const *host) {
     if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to derive the strain rate from");
-    if (b.nx <= 0 || b.ny <= 0 || b.nz <= 0 || b.x0 < 0 || b.y0 < 0 || b.z0 < 0 ||
-        (long long)b.x0 + b.nx > p.nx || (long long)b.y0 + b.ny > p.ny || (long long)b.z0 + b.nz > p.nz)
-        throw lbm_failure(LBM_E_INVALID, "box must be non-empty and inside the domain");
-    int want = 0;
-    for (int i = 0; host && i < LBM3D_STRESS_FIELDS; ++i) want += host[i] ? 1 : 0;
+    check_box(b);
+    const int want = count_wanted(host, LBM3D_STRESS_FIELDS);
     if (want == 0) return;
     stress_args(slabs.at(0), 0, 0, 0, 1, 1, 1);  // omega = 1 is refused before anything is launched or written
     sync_all();
     for (auto &s : slabs) {
-        const int zlo = std::max(b.z0, s.z0), zhi = std::min(b.z0 + b.nz, s.z0 + s.nzs);
-        if (zlo >= zhi) continue;
+        int zlo, zhi;
+        if (!slab_planes(s, b, zlo, zhi)) continue;
         HIP_CHECK(hipSetDevice(s.dev));
         Stress3Args a = stress_args(s, b.x0, b.y0, zlo - s.z0, b.nx, b.ny, zhi - zlo);
-        const size_t rows = (size_t)a.by * a.bz, field_floats = rows * a.sp;
-        const DeviceStage stage(sizeof(float) * field_floats * want);
+        const size_t rows = (size_t)a.by * a.bz;
+        const PlanarStage stage(want, rows * a.sp);
         for (int i = 0, n = 0; i < LBM3D_STRESS_FIELDS; ++i)
-            if (host[i]) a.out[i] = stage.as<float>() + field_floats * n++;
+            if (host[i]) a.out[i] = stage.field(n++);
         HIP_CHECK(stress::launch_neq_strain3d(a, false, s.s_comp));
         HIP_CHECK(hipStreamSynchronize(s.s_comp));
-        const size_t off = (size_t)(zlo - b.z0) * b.ny * b.nx;
-        for (int i = 0; i < LBM3D_STRESS_FIELDS; ++i) {
-            if (!host[i]) continue;
-            if (a.sp == b.nx)  // no row padding: one contiguous copy
-                HIP_CHECK(hipMemcpy(host[i] + off, a.out[i], sizeof(float) * field_floats, hipMemcpyDeviceToHost));
-            else
-                HIP_CHECK(hipMemcpy2D(host[i] + off, sizeof(float) * (size_t)b.nx, a.out[i],
-                                      sizeof(float) * (size_t)a.sp, sizeof(float) * (size_t)b.nx, rows,
-                                      hipMemcpyDeviceToHost));
-        }
+        stage.copy_out(host, LBM3D_STRESS_FIELDS, box_span(b, zlo), (size_t)a.sp, (size_t)b.nx, rows);
     }
 }
 
 // Sum of S:S (fp64) and the largest strain over the local fluid cells; count,
-// fp64 sum and maximum of the strain over the near-wall ones; per-block
-// partials folded here in block order, slab after slab.
+// fp64 sum and maximum of the strain over the near-wall ones, from the kernel's
+// per-block partials (BlockPartials, lbm_diag_host.hpp), slab after slab.
 void lbm3d_handle::stress_stats(double *sum_s2, float *max_strain, int64_t *wall_cells, double *sum_wall_strain,
                                 float *max_wall_strain) {
     if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to take statistics of");
@@ -303,33 +261,23 @@ void lbm3d_handle::stress_stats(double *sum_s2, float *max_strain, int64_t *wall
     stress_args(slabs.at(0), 0, 0, 0, 1, 1, 1);
     sync_all();
     stress_build();
-    double ts = 0.0, tw = 0.0;
-    float ms = 0.f, mw = 0.f;
+    double sum[2] = {0.0, 0.0};  // s2, near-wall strain
+    float max[2] = {0.f, 0.f};   // strain, near-wall strain
     for (size_t k = 0; k < slabs.size(); ++k) {
         const Slab &s = slabs[k];
         HIP_CHECK(hipSetDevice(s.dev));
         Stress3Args a = stress_args(s, 0, 0, 0, p.nx, p.ny, s.nzs);
         a.obst = stress->cls[k];
-        const size_t nb = (size_t)stress::stress3d_blocks(a);
-        const DeviceStage part((sizeof(double) + sizeof(float)) * 2 * nb);  // [2 nb doubles | 2 nb floats]
-        a.sum_part = part.as<double>();
-        a.max_part = reinterpret_cast<float *>(a.sum_part + 2 * nb);
+        const BlockPartials<2, 2> part((size_t)stress::stress3d_blocks(a));
+        a.sum_part = part.sums();
+        a.max_part = part.maxima();
         HIP_CHECK(stress::launch_neq_strain3d(a, true, s.s_comp));
         HIP_CHECK(hipStreamSynchronize(s.s_comp));
-        std::vector<double> hs(2 * nb);
-        std::vector<float> hm(2 * nb);
-        HIP_CHECK(hipMemcpy(hs.data(), a.sum_part, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(hm.data(), a.max_part, sizeof(float) * 2 * nb, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < nb; ++i) {
-            ts += hs[i];
-            tw += hs[nb + i];
-            ms = std::max(ms, hm[i]);
-            mw = std::max(mw, hm[nb + i]);
-        }
+        part.fold(sum, max);
     }
-    if (sum_s2) *sum_s2 = ts;
-    if (max_strain) *max_strain = ms;
+    if (sum_s2) *sum_s2 = sum[0];
+    if (max_strain) *max_strain = max[0];
     if (wall_cells) *wall_cells = stress->wall_cells;
-    if (sum_wall_strain) *sum_wall_strain = tw;
-    if (max_wall_strain) *max_wall_strain = mw;
+    if (sum_wall_strain) *sum_wall_strain = sum[1];
+    if (max_wall_strain) *max_wall_strain = max[1];
 }

@@ -61,7 +61,7 @@ void lbm_handle::avg_sample() {
         const Sub &s = subs[k];
         const avg::Part &q = averages->parts[k];
         set_device(s);
-        const FieldsArgs f = fields_args(s);
+        const LatticeView f = lattice_view(s);
         const avg::MomentArgs a{f.o, f.obst, 0, f.plane, f.pitch, f.w, f.h, f.h, f.sp, f.obst_pressure, q.acc, q.fstride()};
         timed(s, s.s_comp, "accumulate_moments", [&] {
             HIP_CHECK(avg::launch_accumulate<avg::D2Q9Sample>(a, averages->moments == 3, s.s_comp));

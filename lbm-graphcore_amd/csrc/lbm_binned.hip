@@ -4,8 +4,8 @@
 // kernels, then the engine's host side.
 //
 // First pass (binned_sums): one memory-bound pass over the nine populations of
-// the current side of the pair, 37 B read per cell, with macroscopic_fields'
-// addressing: a lane takes four consecutive cells of a row (nine 16-B loads),
+// the current side of the pair, 37 B read per cell, by the access path of
+// lbm_quad.hpp: a lane takes four consecutive cells of a row (nine 16-B loads),
 // a wave 256 columns; the last w % 4 cells of a row go one at a time.  A wave
 // walks one chunk -- at most BN_CHUNK rows inside one bin -- with the fp64 sums
 // of its four columns in registers, then folds along x by bin (fold_x,
@@ -25,15 +25,13 @@
 #include "lbm_binned.hpp"
 #include "lbm_binned_hip.h"
 #include "lbm_engine.hpp"
+#include "lbm_quad.hpp"
 
 namespace lbm {
 namespace binned {
 
-struct Bin2Args {
-    const float *o;        // lattice origin (current side of the pair)
-    const uint8_t *obst;   // uint8[h][w]
-    long long plane;
-    int pitch, w, h;
+// of the view the kernel reads o, obst, plane, pitch, w and h (sp and obst_pressure ride along unused)
+struct Bin2Args : LatticeView {
     Axis x;
     ChunkAxis y;
     int nwx, nslots;       // waves along x; partial slots of a chunk
@@ -63,18 +61,12 @@ __global__ __launch_bounds__(BN_BLOCK) void binned_sums(Bin2Args a) {
             const float *src = a.o + (long long)y * a.pitch + x;
             const uint8_t *ob = a.obst + (long long)y * a.w + x;
             float4 v[Q];
-#pragma unroll
-            for (int k = 0; k < Q; ++k) v[k] = *reinterpret_cast<const float4 *>(src + k * a.plane);
-            unsigned bits;
-            if (obst_word)
-                bits = *reinterpret_cast<const unsigned *>(ob);
-            else
-                bits = (unsigned)ob[0] | ((unsigned)ob[1] << 8) | ((unsigned)ob[2] << 16) | ((unsigned)ob[3] << 24);
+            load_quad<Q>(src, a.plane, v);
+            const unsigned bits = quad_map_bytes(ob, obst_word);
 #pragma unroll
             for (int i = 0; i < BN_QUAD; ++i) {
                 float c[Q];
-#pragma unroll
-                for (int k = 0; k < Q; ++k) c[k] = i == 0 ? v[k].x : i == 1 ? v[k].y : i == 2 ? v[k].z : v[k].w;
+                quad_cell<Q>(v, i, c);
                 add_cell2(c, ((bits >> (8 * i)) & 0xffu) != 0, s[i]);
             }
         }
@@ -87,8 +79,7 @@ __global__ __launch_bounds__(BN_BLOCK) void binned_sums(Bin2Args a) {
             for (int i = 0; i < BN_QUAD - 1; ++i) {
                 if (x + i >= a.w) break;
                 float c[Q];
-#pragma unroll
-                for (int k = 0; k < Q; ++k) c[k] = src[k * a.plane + i];
+                load_cell<Q>(src, a.plane, i, c);
                 add_cell2(c, ob[i] != 0, s[i]);
             }
         }
@@ -205,8 +196,7 @@ void lbm_handle::store_binned(int bw, int bh, double *const *out) {
     using namespace lbm::binned;
     if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to take binned sums of");
     check_bins(p, bw, bh);
-    int want = 0;
-    for (int i = 0; out && i < LBM_BIN_FIELDS; ++i) want += out[i] ? 1 : 0;
+    const int want = count_wanted(out, LBM_BIN_FIELDS);
     if (want == 0) return;
     const int nbx = LBM_BIN_COUNT(p.nx, bw), nby = LBM_BIN_COUNT(p.ny, bh);
     for (int i = 0; i < LBM_BIN_FIELDS; ++i)
@@ -215,14 +205,7 @@ void lbm_handle::store_binned(int bw, int bh, double *const *out) {
     prof_drop();
     for (auto &s : subs) {
         set_device(s);
-        const FieldsArgs f = fields_args(s);
-        Bin2Args a{};
-        a.o = f.o;
-        a.obst = f.obst;
-        a.plane = f.plane;
-        a.pitch = f.pitch;
-        a.w = s.w;
-        a.h = s.h;
+        Bin2Args a{lattice_view(s)};
         a.x = make_axis(s.rect.x0, s.w, bw);
         a.y = make_chunk_axis(s.rect.y0, s.h, bh);
         a.nwx = (s.w + BN_WAVE_COLS - 1) / BN_WAVE_COLS;

@@ -1,7 +1,8 @@
 // lbm_common.hpp -- what the D2Q9 engine (lbm_engine.hpp) and the D3Q19 engine
 // (lbm3d_engine.hpp) share on the host: the failure type behind the LBM_E_*
 // return codes, the HIP / RCCL call checks, the catch-all of the extern "C"
-// layers, and the owner of a device staging allocation.
+// layers, and the owner of a device staging allocation.  What the diagnostics
+// build on it (planar staging, block partials) is in lbm_diag_host.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>

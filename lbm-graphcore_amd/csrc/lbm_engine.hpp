@@ -22,6 +22,8 @@
 //                         choice, launch, residency-failure fallback);
 //   lbm_pipeline_run.hip  step loop of the unfused per-stage pipeline;
 //   lbm_abi.hip           the extern "C" functions.
+// The diagnostics units (fields to binned) share their host paths through
+// lbm_diag_host.hpp and their cell reads and block fold through lbm_quad.hpp.
 //
 // Replaces what the reference delegates to Poplar: graph build and tile
 // mapping (main/LbmAoS.cpp:135-372, main/include/StructuredGridUtils.hpp),
@@ -63,7 +65,7 @@
 #include <array>
 #include <vector>
 
-#include "lbm_common.hpp"
+#include "lbm_diag_host.hpp"
 #include "lbm_hip.h"
 #include "lbm_layout.hpp"
 
@@ -407,7 +409,12 @@ struct lbm_handle {
     size_t aos_pitch(const Sub &s, bool local) const { return sizeof(float) * Q * (size_t)(local ? s.w : p.nx); }
     void load_cells(const float *aos, bool local = false);
     void store(float *aos, float *av, int n_av, bool local = false);
-    FieldsArgs fields_args(const Sub &s) const;
+    // diagnostics (lbm_diag_host.hpp): the current lattice of a sub-domain, and where its rows lie in a
+    // planar host array -- at its rectangle of [ny][nx], or (local) packed after the `packed` cells before it
+    LatticeView lattice_view(const Sub &s) const;
+    HostSpan host_span(const Sub &s, bool local, size_t packed) const {
+        return local ? HostSpan{packed, (size_t)s.w} : HostSpan{(size_t)s.rect.y0 * p.nx + s.rect.x0, (size_t)p.nx};
+    }
     void store_fields(float *ux, float *uy, float *speed, float *pressure, bool local = false);
     void field_stats(double *mass, float *max_speed);
     // momentum-exchange wall forces (lbm_forces.hip; include/lbm_forces_hip.h)

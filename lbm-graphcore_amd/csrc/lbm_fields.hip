@@ -7,10 +7,9 @@
 //
 // Memory-bound: 37 B read (nine populations + the obstacle byte) and at most
 // 16 B written per cell, no reuse, no LDS staging.  One lane takes four
-// consecutive cells of a row: the interior row start is 16-B aligned in both
-// lattice layouts (xoff, plane and pitch are multiples of 4 floats), so that
-// is nine 16-B loads and up to four 16-B stores.  The last w % 4 cells of a
-// row take a scalar path.
+// consecutive cells of a row by the access path of lbm_quad.hpp: nine 16-B
+// loads and up to four 16-B stores; the last w % 4 cells of a row go one at a
+// time.
 //
 // Arithmetic: IEEE fp32, evaluation order of the host function, no
 // contraction (-ffp-contract=off), correctly rounded divide and sqrt (hipcc
@@ -22,6 +21,7 @@
 
 #include "lbm_cell_macro.hpp"
 #include "lbm_engine.hpp"
+#include "lbm_quad.hpp"
 
 namespace lbm {
 
@@ -54,19 +54,13 @@ __global__ __launch_bounds__(BLOCK) void macroscopic_fields(FieldsArgs a) {
         const long long so = (long long)y * a.sp + x;
         if (x + 4 <= a.w) {
             float4 v[Q];
-#pragma unroll
-            for (int k = 0; k < Q; ++k) v[k] = *reinterpret_cast<const float4 *>(src + k * a.plane);
-            unsigned bits;
-            if (obst_word)
-                bits = *reinterpret_cast<const unsigned *>(ob);
-            else
-                bits = (unsigned)ob[0] | ((unsigned)ob[1] << 8) | ((unsigned)ob[2] << 16) | ((unsigned)ob[3] << 24);
+            load_quad<Q>(src, a.plane, v);
+            const unsigned bits = quad_map_bytes(ob, obst_word);
             CellMacro m[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float c[Q];
-#pragma unroll
-                for (int k = 0; k < Q; ++k) c[k] = i == 0 ? v[k].x : i == 1 ? v[k].y : i == 2 ? v[k].z : v[k].w;
+                quad_cell<Q>(v, i, c);
                 const bool blocked = ((bits >> (8 * i)) & 0xffu) != 0;
                 float rho;
                 if (want_u)
@@ -90,8 +84,7 @@ __global__ __launch_bounds__(BLOCK) void macroscopic_fields(FieldsArgs a) {
             // ragged tail of a row: the last w % 4 cells, one at a time
             for (int i = 0; x + i < a.w; ++i) {
                 float c[Q];
-#pragma unroll
-                for (int k = 0; k < Q; ++k) c[k] = src[k * a.plane + i];
+                load_cell<Q>(src, a.plane, i, c);
                 const bool blocked = ob[i] != 0;
                 float rho;
                 CellMacro m;
@@ -113,29 +106,9 @@ __global__ __launch_bounds__(BLOCK) void macroscopic_fields(FieldsArgs a) {
         }
     }
     if (STATS) {
-        // lanes of a wave by shuffle, the block's four waves through LDS: fixed order
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mass += __shfl_down(mass, off, 64);
-            umax = fmaxf(umax, __shfl_down(umax, off, 64));
-        }
-        __shared__ double wmass[BLOCK / 64];
-        __shared__ float wmax[BLOCK / 64];
-        if ((threadIdx.x & 63) == 0) {
-            wmass[threadIdx.x >> 6] = mass;
-            wmax[threadIdx.x >> 6] = umax;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double ms = wmass[0];
-            float mx = wmax[0];
-            for (int i = 1; i < BLOCK / 64; ++i) {
-                ms += wmass[i];
-                mx = fmaxf(mx, wmax[i]);
-            }
-            a.mass_part[blockIdx.x] = ms;
-            a.umax_part[blockIdx.x] = mx;
-        }
+        double s[1] = {mass};
+        float m[1] = {umax};
+        fold_block<BLOCK / 64>(s, m, blockIdx.x, gridDim.x, a.mass_part, a.umax_part);
     }
 }
 
@@ -159,17 +132,8 @@ hipError_t launch_macroscopic_fields(const FieldsArgs &a, bool stats, hipStream_
 
 // ---- D2Q9 engine: host side ----
 
-FieldsArgs lbm_handle::fields_args(const Sub &s) const {
-    FieldsArgs a{};
-    a.o = s.o[s.cur];
-    a.obst = s.obst;
-    a.plane = s.plane;
-    a.pitch = s.pitch;
-    a.w = s.w;
-    a.h = s.h;
-    a.sp = (int)round_up(s.w, 4);
-    a.obst_pressure = p.density * (1.f / 3.f);
-    return a;
+LatticeView lbm_handle::lattice_view(const Sub &s) const {
+    return LatticeView{s.o[s.cur], s.obst, s.plane, s.pitch, s.w, s.h, (int)round_up(s.w, 4), p.density * (1.f / 3.f)};
 }
 
 // u_x, u_y, |u|, pressure of the current lattice into planar
@@ -179,64 +143,47 @@ FieldsArgs lbm_handle::fields_args(const Sub &s) const {
 void lbm_handle::store_fields(float *ux, float *uy, float *speed, float *pressure, bool local) {
     if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to derive fields from");
     float *const host[4] = {ux, uy, speed, pressure};
-    int want = 0;
-    for (float *f : host) want += f ? 1 : 0;
+    const int want = count_wanted(host, 4);
     if (want == 0) return;
     sync_all();
     prof_drop();
     size_t packed = 0;  // local: cells of the sub-domains before this one
     for (auto &s : subs) {
         set_device(s);
-        FieldsArgs a = fields_args(s);
-        const size_t field_floats = (size_t)a.sp * s.h;
-        const DeviceStage stage(sizeof(float) * field_floats * want);
+        FieldsArgs a{lattice_view(s)};
+        const PlanarStage stage(want, (size_t)a.sp * s.h);
         float **dev[4] = {&a.ux, &a.uy, &a.speed, &a.pressure};
         for (int i = 0, n = 0; i < 4; ++i)
-            if (host[i]) *dev[i] = stage.as<float>() + field_floats * n++;
+            if (host[i]) *dev[i] = stage.field(n++);
         timed(s, s.s_comp, "macroscopic_fields", [&] { HIP_CHECK(launch_macroscopic_fields(a, false, s.s_comp)); });
         HIP_CHECK(hipStreamSynchronize(s.s_comp));
-        const size_t off = local ? packed : (size_t)s.rect.y0 * p.nx + s.rect.x0;
-        const size_t pitch = sizeof(float) * (size_t)(local ? s.w : p.nx);
-        for (int i = 0; i < 4; ++i)
-            if (host[i])
-                HIP_CHECK(hipMemcpy2D(host[i] + off, pitch, *dev[i], sizeof(float) * (size_t)a.sp,
-                                      sizeof(float) * (size_t)s.w, (size_t)s.h, hipMemcpyDeviceToHost));
+        stage.copy_out(host, 4, host_span(s, local, packed), (size_t)a.sp, (size_t)s.w, (size_t)s.h);
         packed += (size_t)s.w * s.h;
     }
     prof_collect();
 }
 
 // Total mass (fp64 sum of every local cell's fp32 density) and the largest
-// |u| over the local fluid cells.  The kernel leaves per-block partials;
-// they are folded here in block order, sub-domain after sub-domain, so the
-// same lattice always gives the same bits.
+// |u| over the local fluid cells, from the kernel's per-block partials
+// (BlockPartials, lbm_diag_host.hpp).
 void lbm_handle::field_stats(double *mass, float *max_speed) {
     if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to take statistics of");
     if (!mass && !max_speed) return;
     sync_all();
     prof_drop();
-    double total = 0.0;
-    float umax = 0.f;
+    double total[1] = {0.0};
+    float umax[1] = {0.f};
     for (auto &s : subs) {
         set_device(s);
-        FieldsArgs a = fields_args(s);
-        const int nb = fields_blocks(s.w, s.h);
-        // [nb doubles | nb floats]
-        const DeviceStage part((sizeof(double) + sizeof(float)) * (size_t)nb);
-        std::vector<double> host((size_t)nb + ((size_t)nb + 1) / 2);  // the same block: doubles, then floats
-        a.mass_part = part.as<double>();
-        a.umax_part = reinterpret_cast<float *>(a.mass_part + nb);
+        FieldsArgs a{lattice_view(s)};
+        const BlockPartials<1, 1> part((size_t)fields_blocks(s.w, s.h));
+        a.mass_part = part.sums();
+        a.umax_part = part.maxima();
         timed(s, s.s_comp, "macroscopic_fields stats", [&] { HIP_CHECK(launch_macroscopic_fields(a, true, s.s_comp)); });
         HIP_CHECK(hipStreamSynchronize(s.s_comp));
-        HIP_CHECK(hipMemcpy(host.data(), part.get(), (sizeof(double) + sizeof(float)) * (size_t)nb, hipMemcpyDeviceToHost));
-        std::vector<float> hu((size_t)nb);
-        memcpy(hu.data(), host.data() + nb, sizeof(float) * (size_t)nb);
-        for (int b = 0; b < nb; ++b) {
-            total += host[(size_t)b];
-            umax = std::max(umax, hu[(size_t)b]);
-        }
+        part.fold(total, umax);
     }
     prof_collect();
-    if (mass) *mass = total;
-    if (max_speed) *max_speed = umax;
+    if (mass) *mass = total[0];
+    if (max_speed) *max_speed = umax[0];
 }

@@ -292,26 +292,21 @@ void lbm_handle::store_wall_force(float *fx, float *fy) {
     forces_build();
     prof_drop();
     float *const host[2] = {fx, fy};
-    const int want = (fx ? 1 : 0) + (fy ? 1 : 0);
+    const int want = count_wanted(host, 2);
     for (size_t k = 0; k < subs.size(); ++k) {
         Sub &s = subs[k];
         set_device(s);
         const WallList &wl = forces->lists[k];
         WallArgs a = wl.args(s.o[s.cur], s.plane);
-        const size_t field_floats = (size_t)s.w * s.h;
-        const DeviceStage stage(sizeof(float) * field_floats * want);
-        HIP_CHECK(hipMemsetAsync(stage.get(), 0, sizeof(float) * field_floats * want, s.s_comp));
+        const PlanarStage stage(want, (size_t)s.w * s.h);
+        HIP_CHECK(hipMemsetAsync(stage.get(), 0, stage.bytes(), s.s_comp));
         float **dev[2] = {&a.mx, &a.my};
         for (int i = 0, n = 0; i < 2; ++i)
-            if (host[i]) *dev[i] = stage.as<float>() + field_floats * n++;
+            if (host[i]) *dev[i] = stage.field(n++);
         if (wl.n > 0)
             timed(s, s.s_comp, "wall_force map", [&] { HIP_CHECK(wl.launch(lbm::forces::WALL_MAP, a, s.s_comp)); });
         HIP_CHECK(hipStreamSynchronize(s.s_comp));
-        const size_t off = (size_t)s.rect.y0 * p.nx + s.rect.x0;
-        for (int i = 0; i < 2; ++i)
-            if (host[i])
-                HIP_CHECK(hipMemcpy2D(host[i] + off, sizeof(float) * (size_t)p.nx, *dev[i], sizeof(float) * (size_t)s.w,
-                                      sizeof(float) * (size_t)s.w, (size_t)s.h, hipMemcpyDeviceToHost));
+        stage.copy_out(host, 2, host_span(s, false, 0), (size_t)s.w, (size_t)s.w, (size_t)s.h);
     }
     prof_collect();
 }

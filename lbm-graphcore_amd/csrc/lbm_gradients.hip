@@ -15,7 +15,7 @@
 // velocity_gradients: one memory-bound pass over the nine populations of the
 // current side of the pair (origin / plane / pitch, either layout).  A wave
 // owns a strip of 248 columns and a segment of 32 rows; a lane takes four
-// consecutive cells (nine 16-B loads per row, as macroscopic_fields), keeps
+// consecutive cells (nine 16-B loads per row, lbm_quad.hpp), keeps
 // the velocities of three rows in registers (24 VGPRs) and gets the
 // x-neighbours of its outer cells from the adjacent lanes.  Lanes 0 and 63
 // and one row each side of the segment only supply neighbours: 256 x 34 cells
@@ -31,6 +31,7 @@
 #include "lbm_gradients.hpp"
 #include "lbm_gradients_hip.h"
 #include "lbm_packed.hpp"
+#include "lbm_quad.hpp"
 
 namespace lbm {
 namespace grad {
@@ -72,18 +73,12 @@ __device__ __forceinline__ void load_row(const GradArgs &a, int x, int y, Row &r
     const uint8_t *ob = a.obst + (long long)y * a.w + x;
     if (x >= 0 && x + 4 <= a.w) {
         float4 v[Q];
-#pragma unroll
-        for (int k = 0; k < Q; ++k) v[k] = *reinterpret_cast<const float4 *>(src + k * a.plane);
-        unsigned bits;
-        if ((a.w & 3) == 0)
-            bits = *reinterpret_cast<const unsigned *>(ob);
-        else
-            bits = (unsigned)ob[0] | ((unsigned)ob[1] << 8) | ((unsigned)ob[2] << 16) | ((unsigned)ob[3] << 24);
+        load_quad<Q>(src, a.plane, v);
+        const unsigned bits = quad_map_bytes(ob, (a.w & 3) == 0);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             float c[Q];
-#pragma unroll
-            for (int k = 0; k < Q; ++k) c[k] = i == 0 ? v[k].x : i == 1 ? v[k].y : i == 2 ? v[k].z : v[k].w;
+            quad_cell<Q>(v, i, c);
             const bool blocked = ((bits >> (8 * i)) & 0xffu) != 0;
             if (blocked) r.blocked |= 1u << i;
             cell_velocity(c, blocked, a.obst_pressure, r.ux[i], r.uy[i]);
@@ -100,8 +95,7 @@ __device__ __forceinline__ void load_row(const GradArgs &a, int x, int y, Row &r
             r.uy[i] = e[a.h + y];
         } else if (xc >= 0 && xc < a.w) {
             float c[Q];
-#pragma unroll
-            for (int k = 0; k < Q; ++k) c[k] = src[k * a.plane + i];
+            load_cell<Q>(src, a.plane, i, c);
             const bool blocked = ob[i] != 0;
             if (blocked) r.blocked |= 1u << i;
             cell_velocity(c, blocked, a.obst_pressure, r.ux[i], r.uy[i]);
@@ -131,8 +125,7 @@ __global__ __launch_bounds__(BLOCK) void edge_velocities(GradArgs a) {
     const int y = d == DN ? a.h - 1 : d == DS ? 0 : i;
     const float *src = a.o + (long long)y * a.pitch + x;
     float c[Q];
-#pragma unroll
-    for (int k = 0; k < Q; ++k) c[k] = src[k * a.plane];
+    load_cell<Q>(src, a.plane, 0, c);
     float ux, uy;
     cell_velocity(c, a.obst[(long long)y * a.w + x] != 0, a.obst_pressure, ux, uy);
     float *e = a.edge_out + el.off(d);
@@ -141,7 +134,7 @@ __global__ __launch_bounds__(BLOCK) void edge_velocities(GradArgs a) {
 }
 
 // STATS: no field is stored; block b writes its partial sums and maxima over
-// the fluid cells it owns (fold_stats).
+// the fluid cells it owns (fold_block, lbm_quad.hpp).
 template <bool STATS>
 __global__ __launch_bounds__(BLOCK) void velocity_gradients(GradArgs a) {
     const int lane = threadIdx.x & 63;
@@ -195,7 +188,11 @@ __global__ __launch_bounds__(BLOCK) void velocity_gradients(GradArgs a) {
             c = n;
         }
     }
-    if (STATS) fold_stats<BLOCK / 64>(sw2, ss2, mw, md, blockIdx.x, gridDim.x, a.sum_part, a.max_part);
+    if (STATS) {
+        double s[2] = {sw2, ss2};
+        float m[2] = {mw, md};
+        fold_block<BLOCK / 64>(s, m, blockIdx.x, gridDim.x, a.sum_part, a.max_part);
+    }
 }
 
 int gradient_strips(int w) { return ((w + 3) / 4 + GR_OWN_Q - 1) / GR_OWN_Q; }
@@ -258,17 +255,8 @@ std::vector<GradArgs> lbm_handle::grad_prepare() {
     for (size_t k = 0; k < subs.size(); ++k) {
         const Sub &s = subs[k];
         set_device(s);
-        const FieldsArgs f = fields_args(s);
         const EdgeLayout el{s.w, s.h};
-        GradArgs a{};
-        a.o = f.o;
-        a.obst = f.obst;
-        a.plane = f.plane;
-        a.pitch = f.pitch;
-        a.w = f.w;
-        a.h = f.h;
-        a.sp = f.sp;
-        a.obst_pressure = f.obst_pressure;
+        GradArgs a{lattice_view(s)};
         a.edge_out = gradients->edge[k];
         a.in = gradients->edge[k] + el.total();
         a.strips = grad::gradient_strips(s.w);
@@ -318,8 +306,7 @@ void lbm_handle::grad_release() {
 // neither stored nor staged.
 void lbm_handle::store_gradients(float *const *out, bool local) {
     if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to derive gradients from");
-    int want = 0;
-    for (int i = 0; out && i < LBM_GRAD_FIELDS; ++i) want += out[i] ? 1 : 0;
+    const int want = count_wanted(out, LBM_GRAD_FIELDS);
     if (want == 0) return;
     sync_all();
     prof_drop();
@@ -329,59 +316,43 @@ void lbm_handle::store_gradients(float *const *out, bool local) {
         const Sub &s = subs[k];
         set_device(s);
         GradArgs &a = args[k];
-        const size_t field_floats = (size_t)a.sp * s.h;
-        const DeviceStage stage(sizeof(float) * field_floats * want);
+        const PlanarStage stage(want, (size_t)a.sp * s.h);
         for (int i = 0, n = 0; i < LBM_GRAD_FIELDS; ++i)
-            if (out[i]) a.out[i] = stage.as<float>() + field_floats * n++;
+            if (out[i]) a.out[i] = stage.field(n++);
         timed(s, s.s_comp, "velocity_gradients", [&] { HIP_CHECK(grad::launch_velocity_gradients(a, false, s.s_comp)); });
         HIP_CHECK(hipStreamSynchronize(s.s_comp));
-        const size_t off = local ? packed : (size_t)s.rect.y0 * p.nx + s.rect.x0;
-        const size_t pitch = sizeof(float) * (size_t)(local ? s.w : p.nx);
-        for (int i = 0; i < LBM_GRAD_FIELDS; ++i)
-            if (out[i])
-                HIP_CHECK(hipMemcpy2D(out[i] + off, pitch, a.out[i], sizeof(float) * (size_t)a.sp,
-                                      sizeof(float) * (size_t)s.w, (size_t)s.h, hipMemcpyDeviceToHost));
+        stage.copy_out(out, LBM_GRAD_FIELDS, host_span(s, local, packed), (size_t)a.sp, (size_t)s.w, (size_t)s.h);
         packed += (size_t)s.w * s.h;
     }
     prof_collect();
 }
 
 // Sums of vorticity^2 and S:S (fp64) and the largest |vorticity| and
-// |divergence| over the local fluid cells.  The kernel leaves per-block
-// partials; they are folded here in block order, sub-domain after sub-domain.
+// |divergence| over the local fluid cells, from the kernel's per-block
+// partials (BlockPartials, lbm_diag_host.hpp).
 void lbm_handle::gradient_stats(double *sum_w2, double *sum_s2, float *max_w, float *max_div) {
     if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to take statistics of");
     if (!sum_w2 && !sum_s2 && !max_w && !max_div) return;
     sync_all();
     prof_drop();
     std::vector<GradArgs> args = grad_prepare();
-    double tw = 0.0, ts = 0.0;
-    float mw = 0.f, md = 0.f;
+    double sum[2] = {0.0, 0.0};  // w2, s2
+    float max[2] = {0.f, 0.f};   // |vorticity|, |divergence|
     for (size_t k = 0; k < subs.size(); ++k) {
         const Sub &s = subs[k];
         set_device(s);
         GradArgs &a = args[k];
-        const size_t nb = (size_t)grad::gradient_blocks(s.w, s.h);
-        const DeviceStage part((sizeof(double) + sizeof(float)) * 2 * nb);  // [2 nb doubles | 2 nb floats]
-        a.sum_part = part.as<double>();
-        a.max_part = reinterpret_cast<float *>(a.sum_part + 2 * nb);
+        const BlockPartials<2, 2> part((size_t)grad::gradient_blocks(s.w, s.h));
+        a.sum_part = part.sums();
+        a.max_part = part.maxima();
         timed(s, s.s_comp, "velocity_gradients stats",
               [&] { HIP_CHECK(grad::launch_velocity_gradients(a, true, s.s_comp)); });
         HIP_CHECK(hipStreamSynchronize(s.s_comp));
-        std::vector<double> hs(2 * nb);
-        std::vector<float> hm(2 * nb);
-        HIP_CHECK(hipMemcpy(hs.data(), a.sum_part, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(hm.data(), a.max_part, sizeof(float) * 2 * nb, hipMemcpyDeviceToHost));
-        for (size_t b = 0; b < nb; ++b) {
-            tw += hs[b];
-            ts += hs[nb + b];
-            mw = std::max(mw, hm[b]);
-            md = std::max(md, hm[nb + b]);
-        }
+        part.fold(sum, max);
     }
     prof_collect();
-    if (sum_w2) *sum_w2 = tw;
-    if (sum_s2) *sum_s2 = ts;
-    if (max_w) *max_w = mw;
-    if (max_div) *max_div = md;
+    if (sum_w2) *sum_w2 = sum[0];
+    if (sum_s2) *sum_s2 = sum[1];
+    if (max_w) *max_w = max[0];
+    if (max_div) *max_div = max[1];
 }

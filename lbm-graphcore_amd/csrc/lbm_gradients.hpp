@@ -1,7 +1,6 @@
 // lbm_gradients.hpp -- what the velocity-gradient kernels of both engines share
 // (lbm_gradients.hip, lbm3d_gradients.hip; include/lbm_gradients_hip.h): the
-// per-cell expressions of the definition, the argument blocks of the kernels,
-// and the fixed-order fold of the statistics.
+// per-cell expressions of the definition and the argument blocks of the kernels.
 //
 // Arithmetic: IEEE fp32 in the order the header writes, no contraction
 // (-ffp-contract=off), correctly rounded sqrt (hipcc default).  The inputs are
@@ -12,6 +11,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "lbm_views.hpp"
 
 namespace lbm {
 namespace grad {
@@ -56,13 +57,7 @@ struct EdgeLayout {
     __host__ __device__ long long total() const { return 4LL * h + 4LL * w; }
 };
 
-struct GradArgs {
-    const float *o;        // lattice origin (current side of the pair)
-    const uint8_t *obst;   // uint8[h][w]
-    long long plane;
-    int pitch, w, h;
-    int sp;                // staging row pitch: roundup(w, 4)
-    float obst_pressure;
+struct GradArgs : LatticeView {
     const float *in;       // edge velocities across the four sides (EdgeLayout)
     float *edge_out;       // edge kernel: this sub-domain's own edges (EdgeLayout)
     float *out[4];         // LBM_GRAD_* staging arrays float[h][sp]; a null array is not stored
@@ -100,16 +95,9 @@ __device__ __forceinline__ Grad3 gradients3(const float (&px)[3], const float (&
     return g;
 }
 
-struct Grad3Args {
-    const float *o;        // lattice origin: plane z = 0 of the slab
-    const uint8_t *obst;   // uint8[nzs][ny][nx]
-    long long PL, KS;
-    int px, nx, ny, nzs;
-    int x0, y0, z0;        // box origin (z0 slab-local)
-    int bx, by, bz;        // box extents (> 0, inside the slab)
-    int quad;              // x0 % 4 == 0: a lane's four cells are one aligned 16 B
-    int sp;                // staging row pitch (floats): roundup(bx, 4)
-    float obst_pressure;
+// the view with quad = (x0 % 4 == 0) and sp = roundup(bx, 4) whatever the box width
+struct Grad3Args : Box3View {
+    int nzs;               // planes of the slab
     // velocities of the planes beyond the slab: below (z = -1) and above (z = nzs),
     // planar [3][ny][hp] each (ux, uy, uz)
     const float *below, *above;
@@ -118,43 +106,6 @@ struct Grad3Args {
     double *sum_part;      // stats: [2][blocks]
     float *max_part;       // stats: [2][blocks]
 };
-
-// Fold of a block's per-lane statistics in a fixed order (lanes of a wave by
-// shuffle, the waves through LDS); thread 0 writes the block's partials.
-template <int WAVES>
-__device__ __forceinline__ void fold_stats(double sw2, double ss2, float mw, float md, long long block,
-                                           long long blocks, double *sum_part, float *max_part) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        sw2 += __shfl_down(sw2, off, 64);
-        ss2 += __shfl_down(ss2, off, 64);
-        mw = fmaxf(mw, __shfl_down(mw, off, 64));
-        md = fmaxf(md, __shfl_down(md, off, 64));
-    }
-    __shared__ double ws[2][WAVES];
-    __shared__ float wm[2][WAVES];
-    if ((threadIdx.x & 63) == 0) {
-        ws[0][threadIdx.x >> 6] = sw2;
-        ws[1][threadIdx.x >> 6] = ss2;
-        wm[0][threadIdx.x >> 6] = mw;
-        wm[1][threadIdx.x >> 6] = md;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = ws[0][0], b = ws[1][0];
-        float c = wm[0][0], d = wm[1][0];
-        for (int i = 1; i < WAVES; ++i) {
-            a += ws[0][i];
-            b += ws[1][i];
-            c = fmaxf(c, wm[0][i]);
-            d = fmaxf(d, wm[1][i]);
-        }
-        sum_part[block] = a;
-        sum_part[blocks + block] = b;
-        max_part[block] = c;
-        max_part[blocks + block] = d;
-    }
-}
 
 }  // namespace grad
 }  // namespace lbm

@@ -30,6 +30,8 @@
 
 #include <cstdint>
 
+#include "lbm_views.hpp"
+
 namespace lbm {
 
 constexpr int Q = 9;
@@ -245,12 +247,7 @@ struct HaloArgs {
 
 // Macroscopic fields of the current lattice (lbm_fields.hip): planar staging
 // arrays float[h][sp], sp = roundup(w, 4); a null array is not computed.
-struct FieldsArgs {
-    const float *o;         // lattice origin
-    const uint8_t *obst;    // uint8[h][w]
-    long long plane;
-    int pitch, w, h, sp;
-    float obst_pressure;    // pressure reported for an obstacle cell: density * (1/3)
+struct FieldsArgs : LatticeView {
     float *ux, *uy, *speed, *pressure;
     double *mass_part;      // stats launch: per-block fp64 sums of the cells' densities
     float *umax_part;       // stats launch: per-block max |u| over fluid cells

@@ -11,9 +11,9 @@
 // accumulate_moments is memory-bound: per cell and sample it reads the Q
 // populations and the obstacle byte (37 B / 77 B) and reads and writes 8 B of
 // every accumulator: 85 B (MEAN) or 149 B (MEAN|SECOND) for D2Q9, 141 B or
-// 253 B for D3Q19.  One lane takes four consecutive cells of a row, as
-// macroscopic_fields does: Q 16-B loads, the obstacle word, and per field 32
-// contiguous, 32-B aligned accumulator bytes (two 16-B loads, two 16-B
+// 253 B for D3Q19.  One lane takes four consecutive cells of a row by the
+// access path of lbm_quad.hpp: Q 16-B loads, the obstacle word, and per field
+// 32 contiguous, 32-B aligned accumulator bytes (two 16-B loads, two 16-B
 // stores).  No atomics, no LDS: every accumulator has one owner lane.
 #pragma once
 
@@ -23,7 +23,8 @@
 #include <cstdint>
 #include <vector>
 
-#include "lbm_common.hpp"
+#include "lbm_diag_host.hpp"
+#include "lbm_quad.hpp"
 
 namespace lbm {
 
@@ -95,19 +96,13 @@ __global__ __launch_bounds__(AVG_BLOCK) void accumulate_moments(MomentArgs a) {
         double *acc = a.acc + (long long)r * a.sp + x;
         if (x + 4 <= a.w) {
             float4 v[Q];
-#pragma unroll
-            for (int k = 0; k < Q; ++k) v[k] = *reinterpret_cast<const float4 *>(src + k * a.KS);
-            unsigned bits;
-            if (obst_word)
-                bits = *reinterpret_cast<const unsigned *>(ob);
-            else
-                bits = (unsigned)ob[0] | ((unsigned)ob[1] << 8) | ((unsigned)ob[2] << 16) | ((unsigned)ob[3] << 24);
+            load_quad<Q>(src, a.KS, v);
+            const unsigned bits = quad_map_bytes(ob, obst_word);
             double d[4][NV + 1];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float c[Q], m[NV + 1];
-#pragma unroll
-                for (int k = 0; k < Q; ++k) c[k] = i == 0 ? v[k].x : i == 1 ? v[k].y : i == 2 ? v[k].z : v[k].w;
+                quad_cell<Q>(v, i, c);
                 T::sample(c, ((bits >> (8 * i)) & 0xffu) != 0, a.obst_pressure, m);
 #pragma unroll
                 for (int f = 0; f <= NV; ++f) d[i][f] = (double)m[f];
@@ -129,8 +124,7 @@ __global__ __launch_bounds__(AVG_BLOCK) void accumulate_moments(MomentArgs a) {
             // ragged tail of a row: the last w % 4 cells, one at a time
             for (int i = 0; x + i < a.w; ++i) {
                 float c[Q], m[NV + 1];
-#pragma unroll
-                for (int k = 0; k < Q; ++k) c[k] = src[k * a.KS + i];
+                load_cell<Q>(src, a.KS, i, c);
                 T::sample(c, ob[i] != 0, a.obst_pressure, m);
                 add_cell<T, SECOND>(m, acc + i, a.fstride);
             }
@@ -327,23 +321,18 @@ void store_means(const State *st, float *const *out, L &&launch) {
     for (size_t k = 0; k < st->parts.size(); ++k) {
         const Part &p = st->parts[k];
         HIP_CHECK(hipSetDevice(p.dev));
-        const size_t field_floats = (size_t)p.fstride();
-        const DeviceStage stage(sizeof(float) * field_floats * want);
+        const PlanarStage stage(want, (size_t)p.fstride());
         MeansArgs m{};
         m.acc = p.acc;
         m.fstride = p.fstride();
         m.n = (double)st->n;
         for (int f = 0, i = 0; f < st->nf; ++f) {
             field_sums(st->nv, f, m.a[f], m.b[f], m.ab[f]);
-            if (out[f]) m.out[f] = stage.as<float>() + field_floats * i++;
+            if (out[f]) m.out[f] = stage.field(i++);
         }
         launch(k, p, m);
         HIP_CHECK(hipStreamSynchronize(p.st));
-        for (int f = 0; f < st->nf; ++f)
-            if (out[f])
-                HIP_CHECK(hipMemcpy2D(out[f] + p.host_off, sizeof(float) * p.host_pitch, m.out[f],
-                                      sizeof(float) * (size_t)p.sp, sizeof(float) * (size_t)p.w, (size_t)p.rows,
-                                      hipMemcpyDeviceToHost));
+        stage.copy_out(out, st->nf, HostSpan{p.host_off, p.host_pitch}, (size_t)p.sp, (size_t)p.w, (size_t)p.rows);
     }
 }
 

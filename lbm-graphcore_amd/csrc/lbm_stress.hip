@@ -8,8 +8,8 @@
 // populations of the current side of the pair (origin / plane / pitch, either
 // layout): 37 B read per cell, 4 B written per requested field, no LDS but the
 // statistics' fold.  A lane takes four consecutive cells of a row (nine 16-B
-// loads, a float4 store per field, as macroscopic_fields) and ST_ITER such
-// quads a block apart; the last w % 4 cells of a row take a scalar path.
+// loads, lbm_quad.hpp; a float4 store per field) and ST_ITER such quads a
+// block apart; the last w % 4 cells of a row go one at a time.
 //
 // Near-wall cells are a property of the obstacle map alone: the statistics
 // read a class map (CLS_*) in place of the obstacle map, built on the host
@@ -20,7 +20,7 @@
 #include <algorithm>
 
 #include "lbm_engine.hpp"
-#include "lbm_gradients.hpp"
+#include "lbm_quad.hpp"
 #include "lbm_stress.hpp"
 #include "lbm_stress_hip.h"
 
@@ -28,7 +28,7 @@ namespace lbm {
 namespace stress {
 
 // STATS: no field is stored and a.obst is the class map; block b writes its
-// partial sums and maxima over the fluid cells it owns (grad::fold_stats).
+// partial sums and maxima over the fluid cells it owns (fold_block, lbm_quad.hpp).
 template <bool STATS>
 __global__ __launch_bounds__(ST_BLOCK) void neq_strain(StressArgs a) {
     const int qpr = (a.w + 3) >> 2;  // lanes' quads per row
@@ -47,19 +47,14 @@ __global__ __launch_bounds__(ST_BLOCK) void neq_strain(StressArgs a) {
         const long long so = (long long)y * a.sp + x;
         if (x + 4 <= a.w) {
             float4 v[Q];
-#pragma unroll
-            for (int k = 0; k < Q; ++k) v[k] = *reinterpret_cast<const float4 *>(src + k * a.plane);
-            unsigned bits;
-            if (obst_word)
-                bits = *reinterpret_cast<const unsigned *>(ob);
-            else
-                bits = (unsigned)ob[0] | ((unsigned)ob[1] << 8) | ((unsigned)ob[2] << 16) | ((unsigned)ob[3] << 24);
+            // the store variant walks (12 SGPRs fewer), the stats variant indexes (2 VGPRs fewer): lbm_quad.hpp
+            load_quad<Q, !STATS>(src, a.plane, v);
+            const unsigned bits = quad_map_bytes(ob, obst_word);
             Strain2 s[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float c[Q];
-#pragma unroll
-                for (int k = 0; k < Q; ++k) c[k] = i == 0 ? v[k].x : i == 1 ? v[k].y : i == 2 ? v[k].z : v[k].w;
+                quad_cell<Q>(v, i, c);
                 const unsigned cls = (bits >> (8 * i)) & 0xffu;
                 const bool blocked = STATS ? cls == CLS_BLOCKED : cls != 0;
                 s[i] = neq_strain2(c, blocked, a.coef);
@@ -84,8 +79,7 @@ __global__ __launch_bounds__(ST_BLOCK) void neq_strain(StressArgs a) {
             // ragged tail of a row: the last w % 4 cells, one at a time
             for (int i = 0; x + i < a.w; ++i) {
                 float c[Q];
-#pragma unroll
-                for (int k = 0; k < Q; ++k) c[k] = src[k * a.plane + i];
+                load_cell<Q>(src, a.plane, i, c);
                 const unsigned cls = ob[i];
                 const bool blocked = STATS ? cls == CLS_BLOCKED : cls != 0;
                 const Strain2 s = neq_strain2(c, blocked, a.coef);
@@ -106,9 +100,11 @@ __global__ __launch_bounds__(ST_BLOCK) void neq_strain(StressArgs a) {
             }
         }
     }
-    if (STATS)
-        grad::fold_stats<ST_BLOCK / 64>(sum_s2, sum_wall, max_s, max_wall, blockIdx.x, gridDim.x, a.sum_part,
-                                        a.max_part);
+    if (STATS) {
+        double s[2] = {sum_s2, sum_wall};
+        float m[2] = {max_s, max_wall};
+        fold_block<ST_BLOCK / 64>(s, m, blockIdx.x, gridDim.x, a.sum_part, a.max_part);
+    }
 }
 
 // blocks of a launch over w x h: also the partials a stats launch writes
@@ -142,21 +138,8 @@ using lbm::stress::StressArgs;
 
 // the arguments of sub-domain s but the outputs; refuses omega = 1
 StressArgs lbm_handle::stress_args(const Sub &s) const {
-    const float omo = 1.f - p.omega;
-    if (omo == 0.f)
-        throw lbm_failure(LBM_E_INVALID,
-                          "omega = 1: the post-collision lattice carries no non-equilibrium part to take the strain "
-                          "rate from");
-    const FieldsArgs f = fields_args(s);
-    StressArgs a{};
-    a.o = f.o;
-    a.obst = f.obst;
-    a.plane = f.plane;
-    a.pitch = f.pitch;
-    a.w = f.w;
-    a.h = f.h;
-    a.sp = f.sp;
-    a.coef = (-1.5f * p.omega) / omo;
+    StressArgs a{lattice_view(s)};
+    a.coef = neq_strain_coef(p.omega);
     return a;
 }
 
@@ -212,8 +195,7 @@ void lbm_handle::stress_release() {
 // stored nor staged.
 void lbm_handle::store_stress(float *const *out, bool local) {
     if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to derive the strain rate from");
-    int want = 0;
-    for (int i = 0; out && i < LBM_STRESS_FIELDS; ++i) want += out[i] ? 1 : 0;
+    const int want = count_wanted(out, LBM_STRESS_FIELDS);
     if (want == 0) return;
     stress_args(subs.at(0));  // omega = 1 is refused before anything is launched or written
     sync_all();
@@ -222,27 +204,20 @@ void lbm_handle::store_stress(float *const *out, bool local) {
     for (auto &s : subs) {
         set_device(s);
         StressArgs a = stress_args(s);
-        const size_t field_floats = (size_t)a.sp * s.h;
-        const DeviceStage stage(sizeof(float) * field_floats * want);
+        const PlanarStage stage(want, (size_t)a.sp * s.h);
         for (int i = 0, n = 0; i < LBM_STRESS_FIELDS; ++i)
-            if (out[i]) a.out[i] = stage.as<float>() + field_floats * n++;
+            if (out[i]) a.out[i] = stage.field(n++);
         timed(s, s.s_comp, "neq_strain", [&] { HIP_CHECK(stress::launch_neq_strain(a, false, s.s_comp)); });
         HIP_CHECK(hipStreamSynchronize(s.s_comp));
-        const size_t off = local ? packed : (size_t)s.rect.y0 * p.nx + s.rect.x0;
-        const size_t pitch = sizeof(float) * (size_t)(local ? s.w : p.nx);
-        for (int i = 0; i < LBM_STRESS_FIELDS; ++i)
-            if (out[i])
-                HIP_CHECK(hipMemcpy2D(out[i] + off, pitch, a.out[i], sizeof(float) * (size_t)a.sp,
-                                      sizeof(float) * (size_t)s.w, (size_t)s.h, hipMemcpyDeviceToHost));
+        stage.copy_out(out, LBM_STRESS_FIELDS, host_span(s, local, packed), (size_t)a.sp, (size_t)s.w, (size_t)s.h);
         packed += (size_t)s.w * s.h;
     }
     prof_collect();
 }
 
 // Sum of S:S (fp64) and the largest strain over the local fluid cells; count,
-// fp64 sum and maximum of the strain over the near-wall ones.  The kernel
-// leaves per-block partials; they are folded here in block order, sub-domain
-// after sub-domain.
+// fp64 sum and maximum of the strain over the near-wall ones, from the
+// kernel's per-block partials (BlockPartials, lbm_diag_host.hpp).
 void lbm_handle::stress_stats(double *sum_s2, float *max_strain, int64_t *wall_cells, double *sum_wall_strain,
                               float *max_wall_strain) {
     if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to take statistics of");
@@ -251,34 +226,24 @@ void lbm_handle::stress_stats(double *sum_s2, float *max_strain, int64_t *wall_c
     sync_all();
     stress_build();
     prof_drop();
-    double ts = 0.0, tw = 0.0;
-    float ms = 0.f, mw = 0.f;
+    double sum[2] = {0.0, 0.0};  // s2, near-wall strain
+    float max[2] = {0.f, 0.f};   // strain, near-wall strain
     for (size_t k = 0; k < subs.size(); ++k) {
         const Sub &s = subs[k];
         set_device(s);
         StressArgs a = stress_args(s);
         a.obst = stress->cls[k];
-        const size_t nb = (size_t)stress::stress_blocks(s.w, s.h);
-        const DeviceStage part((sizeof(double) + sizeof(float)) * 2 * nb);  // [2 nb doubles | 2 nb floats]
-        a.sum_part = part.as<double>();
-        a.max_part = reinterpret_cast<float *>(a.sum_part + 2 * nb);
+        const BlockPartials<2, 2> part((size_t)stress::stress_blocks(s.w, s.h));
+        a.sum_part = part.sums();
+        a.max_part = part.maxima();
         timed(s, s.s_comp, "neq_strain stats", [&] { HIP_CHECK(stress::launch_neq_strain(a, true, s.s_comp)); });
         HIP_CHECK(hipStreamSynchronize(s.s_comp));
-        std::vector<double> hs(2 * nb);
-        std::vector<float> hm(2 * nb);
-        HIP_CHECK(hipMemcpy(hs.data(), a.sum_part, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(hm.data(), a.max_part, sizeof(float) * 2 * nb, hipMemcpyDeviceToHost));
-        for (size_t b = 0; b < nb; ++b) {
-            ts += hs[b];
-            tw += hs[nb + b];
-            ms = std::max(ms, hm[b]);
-            mw = std::max(mw, hm[nb + b]);
-        }
+        part.fold(sum, max);
     }
     prof_collect();
-    if (sum_s2) *sum_s2 = ts;
-    if (max_strain) *max_strain = ms;
+    if (sum_s2) *sum_s2 = sum[0];
+    if (max_strain) *max_strain = max[0];
     if (wall_cells) *wall_cells = stress->wall_cells;
-    if (sum_wall_strain) *sum_wall_strain = tw;
-    if (max_wall_strain) *max_wall_strain = mw;
+    if (sum_wall_strain) *sum_wall_strain = sum[1];
+    if (max_wall_strain) *max_wall_strain = max[1];
 }

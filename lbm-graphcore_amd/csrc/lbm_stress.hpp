@@ -15,6 +15,7 @@
 
 #include "lbm3d_cell_macro.hpp"
 #include "lbm_cell_macro.hpp"
+#include "lbm_views.hpp"
 
 namespace lbm {
 namespace stress {
@@ -37,7 +38,7 @@ struct Strain2 {
     float sxx, sxy, syy, strain, s2;
 };
 
-// coef = (-1.5f * omega) / (1.f - omega), formed once on the host in fp32
+// coef = (-1.5f * omega) / (1.f - omega), formed once on the host in fp32 (neq_strain_coef, lbm_diag_host.hpp)
 __device__ __forceinline__ Strain2 neq_strain2(const float (&c)[9], bool blocked, float coef) {
     Strain2 s{0.f, 0.f, 0.f, 0.f, 0.f};
     if (blocked) return s;
@@ -59,13 +60,9 @@ __device__ __forceinline__ Strain2 neq_strain2(const float (&c)[9], bool blocked
     return s;
 }
 
-struct StressArgs {
-    const float *o;        // lattice origin (current side of the pair)
-    const uint8_t *obst;   // uint8[h][w]: the obstacle map (store), or the class map CLS_* (stats)
-    long long plane;
-    int pitch, w, h;
-    int sp;                // staging row pitch: roundup(w, 4)
-    float coef;
+// obst: the obstacle map (store), or the class map CLS_* (stats)
+struct StressArgs : LatticeView {
+    float coef;            // neq_strain_coef(omega)
     float *out[4];         // LBM_STRESS_* staging arrays float[h][sp]; a null array is not stored
     double *sum_part;      // stats: [2][blocks] fp64 partial sums (s2, then near-wall strain)
     float *max_part;       // stats: [2][blocks] partial maxima (strain, then near-wall strain)
@@ -111,16 +108,9 @@ __device__ __forceinline__ Strain3 neq_strain3(const float (&c)[19], bool blocke
     return s;
 }
 
-struct Stress3Args {
-    const float *o;        // lattice origin: plane z = 0 of the slab
-    const uint8_t *obst;   // uint8[nzs][ny][nx]: the obstacle map (store), or the class map CLS_* (stats)
-    long long PL, KS;
-    int px, nx, ny;
-    int x0, y0, z0;        // box origin (z0 slab-local)
-    int bx, by, bz;        // box extents (> 0, inside the slab)
-    int quad;              // x0 % 4 == 0 and bx >= 4: a lane's four cells are one aligned 16 B
-    int sp;                // staging row pitch (floats): roundup(bx, 4) on the quad path, else bx
-    float coef;
+// obst: the obstacle map (store), or the class map CLS_* (stats)
+struct Stress3Args : Box3View {
+    float coef;            // neq_strain_coef(omega)
     float *out[7];         // LBM3D_STRESS_* staging arrays float[bz][by][sp]; a null array is not stored
     double *sum_part;      // stats: [2][blocks]
     float *max_part;       // stats: [2][blocks]
