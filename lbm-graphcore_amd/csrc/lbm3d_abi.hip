@@ -2,7 +2,7 @@
 // include/lbm3d_fields_hip.h and the D3Q19 functions of
 // include/lbm_forces_hip.h, include/lbm_averages_hip.h and
 // include/lbm_gradients_hip.h, include/lbm_stress_hip.h and
-// include/lbm_binned_hip.h over the engine
+// include/lbm_binned_hip.h and include/lbm_tracers_hip.h over the engine
 // (lbm3d_engine.hpp), and the posting order of its RCCL ghost exchange.
 
 #include "lbm3d_engine.hpp"
@@ -10,6 +10,7 @@
 #include "lbm_binned_hip.h"
 #include "lbm_gradients_hip.h"
 #include "lbm_stress_hip.h"
+#include "lbm_tracers_hip.h"
 
 namespace lbm {
 std::array<lbm_xfer, 4> slab_posts(int rank, int world, long long floats) {
@@ -175,6 +176,38 @@ int lbm3d_store_binned(lbm3d_handle *h, int32_t bw, int32_t bh, int32_t bd, doub
 int lbm3d_bin_fluid_cells(lbm3d_handle *h, int32_t bw, int32_t bh, int32_t bd, int64_t *count) {
     if (!h) return LBM_E_INVALID;
     return guarded(h, [&] { h->bin_fluid_cells(bw, bh, bd, count); });
+}
+
+int lbm3d_tracer_begin(lbm3d_handle *h, int64_t n, const double *x, const double *y, const double *z) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->tracer_begin(n, x, y, z); });
+}
+
+int lbm3d_tracer_count(lbm3d_handle *h, int64_t *n) {
+    if (!h || !n) return LBM_E_INVALID;
+    return guarded(h, [&] { *n = h->tracer_count(); });
+}
+
+int lbm3d_tracer_advance(lbm3d_handle *h, double dt, int32_t scheme) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->tracer_advance(dt, scheme); });
+}
+
+int lbm3d_tracer_sample(lbm3d_handle *h, double *ux, double *uy, double *uz, double *pressure) {
+    if (!h) return LBM_E_INVALID;
+    double *const host[4] = {ux, uy, uz, pressure};
+    return guarded(h, [&] { h->tracer_sample(host); });
+}
+
+int lbm3d_tracer_store(lbm3d_handle *h, double *x, double *y, double *z, uint8_t *blocked) {
+    if (!h) return LBM_E_INVALID;
+    double *const host[3] = {x, y, z};
+    return guarded(h, [&] { h->tracer_store(host, blocked); });
+}
+
+int lbm3d_tracer_end(lbm3d_handle *h) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->tracer_end(); });
 }
 
 int lbm3d_last_run_seconds(lbm3d_handle *h, double *seconds) {

@@ -691,6 +691,7 @@ void lbm3d_handle::store(float *aos, float *av, int n_av) {
 void lbm3d_handle::destroy() {
     walls_release();
     avg_end();
+    tracer_end();
     grad_release();
     stress_release();
     for (auto &s : slabs) {

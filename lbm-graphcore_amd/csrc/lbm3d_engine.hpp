@@ -10,6 +10,7 @@
 //   lbm3d_gradients.hip vorticity, divergence, strain rate and Q (kernel + host side);
 //   lbm3d_stress.hip   strain rate and wall shear from the non-equilibrium moments (kernel + host side);
 //   lbm3d_binned.hip   sums over box-shaped bins of the current lattice (kernel + host side);
+//   lbm3d_tracers.hip  Lagrangian tracers and point probes (host side; kernels in lbm_tracers.hpp);
 //   lbm3d_abi.hip      the extern "C" functions and the RCCL posting order.
 // The diagnostics units (fields to binned) share their host paths through
 // lbm_diag_host.hpp and their cell reads and block fold through lbm_quad.hpp.
@@ -33,6 +34,9 @@ namespace lbm {
 
 namespace avg {
 struct State;  // accumulators of a handle that is averaging (lbm_moments.hpp)
+}
+namespace tracer {
+struct State;  // point set of a handle that keeps tracers (lbm_tracers.hpp)
 }
 namespace grad {
 struct Grad3Args;  // lbm_gradients.hpp
@@ -269,4 +273,12 @@ struct lbm3d_handle {
     // lbm3d_binned.hip (include/lbm_binned_hip.h)
     void store_binned(int bw, int bh, int bd, double *const *out);
     void bin_fluid_cells(int bw, int bh, int bd, int64_t *count);
+    // lbm3d_tracers.hip (include/lbm_tracers_hip.h)
+    lbm::tracer::State *tracers = nullptr;  // set between tracer_begin and tracer_end
+    void tracer_begin(int64_t n, const double *x, const double *y, const double *z);
+    int64_t tracer_count() const;
+    void tracer_advance(double dt, int scheme);
+    void tracer_sample(double *const (&host)[4]);
+    void tracer_store(double *const (&host)[3], uint8_t *blocked);
+    void tracer_end();
 };

@@ -1,7 +1,7 @@
 // lbm_abi.hip -- the extern "C" functions of include/lbm_hip.h and the D2Q9
 // functions of include/lbm_forces_hip.h, include/lbm_averages_hip.h and
 // include/lbm_gradients_hip.h, include/lbm_stress_hip.h and
-// include/lbm_binned_hip.h over the engine.
+// include/lbm_binned_hip.h and include/lbm_tracers_hip.h over the engine.
 
 #include "lbm_averages_hip.h"
 #include "lbm_binned_hip.h"
@@ -9,6 +9,7 @@
 #include "lbm_forces_hip.h"
 #include "lbm_gradients_hip.h"
 #include "lbm_stress_hip.h"
+#include "lbm_tracers_hip.h"
 
 // --------------------------------------------------------------------------
 // C ABI
@@ -259,6 +260,36 @@ int lbm_store_binned(lbm_handle *h, int32_t bw, int32_t bh, double *const out[LB
 int lbm_bin_fluid_cells(lbm_handle *h, int32_t bw, int32_t bh, int64_t *count) {
     if (!h) return LBM_E_INVALID;
     return guarded(h, [&] { h->bin_fluid_cells(bw, bh, count); });
+}
+
+int lbm_tracer_begin(lbm_handle *h, int64_t n, const double *x, const double *y) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->tracer_begin(n, x, y); });
+}
+
+int lbm_tracer_count(lbm_handle *h, int64_t *n) {
+    if (!h || !n) return LBM_E_INVALID;
+    return guarded(h, [&] { *n = h->tracer_count(); });
+}
+
+int lbm_tracer_advance(lbm_handle *h, double dt, int32_t scheme) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->tracer_advance(dt, scheme); });
+}
+
+int lbm_tracer_sample(lbm_handle *h, double *ux, double *uy, double *pressure) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->tracer_sample(ux, uy, pressure); });
+}
+
+int lbm_tracer_store(lbm_handle *h, double *x, double *y, uint8_t *blocked) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->tracer_store(x, y, blocked); });
+}
+
+int lbm_tracer_end(lbm_handle *h) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->tracer_end(); });
 }
 
 int64_t lbm_local_cells(lbm_handle *h) {

@@ -928,6 +928,7 @@ void lbm_handle::destroy() {
     prof_release();
     forces_release();
     avg_end();
+    tracer_end();
     grad_release();
     stress_release();
     for (auto &s : subs) {

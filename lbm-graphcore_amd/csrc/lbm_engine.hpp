@@ -14,6 +14,9 @@
 //                         moments of the current lattice (kernel and its host side);
 //   lbm_binned.hip        sums over rectangular bins of the current lattice
 //                         (kernels and their host side);
+//   lbm_tracers.hip       Lagrangian tracers and point probes: a point set
+//                         on the device, interpolated from the current
+//                         lattice (host side; kernels in lbm_tracers.hpp);
 //   lbm_exchange.hip      partition rule, torus neighbours, halo destinations,
 //                         the posted exchange (RCCL or device copies);
 //   lbm_split.hip         work decomposition: boundary / interior split,
@@ -109,6 +112,9 @@ struct State;  // accumulators of a handle that is averaging (lbm_moments.hpp)
 namespace grad {
 struct State;     // edge-velocity buffers of a handle that asked for gradients (lbm_gradients.hip)
 struct GradArgs;  // lbm_gradients.hpp
+}
+namespace tracer {
+struct State;  // point set of a handle that keeps tracers (lbm_tracers.hpp)
 }
 namespace stress {
 struct State;       // near-wall class maps of a handle that asked for strain statistics (lbm_stress.hip)
@@ -451,5 +457,13 @@ struct lbm_handle {
     // binned sums (lbm_binned.hip; include/lbm_binned_hip.h)
     void store_binned(int bw, int bh, double *const *out);
     void bin_fluid_cells(int bw, int bh, int64_t *count);
+    // tracers and point probes (lbm_tracers.hip; include/lbm_tracers_hip.h)
+    lbm::tracer::State *tracers = nullptr;  // set between tracer_begin and tracer_end
+    void tracer_begin(int64_t n, const double *x, const double *y);
+    int64_t tracer_count() const;
+    void tracer_advance(double dt, int scheme);
+    void tracer_sample(double *ux, double *uy, double *pressure);
+    void tracer_store(double *x, double *y, uint8_t *blocked);
+    void tracer_end();
     void destroy();
 };

@@ -67,11 +67,12 @@ class Engine {
 
     // run(1): the conditional first acceleration (LastChance.cpp:161-183),
     // then `steps` fused steps; av_vels[t] per step.  Returns wall seconds of
-    // the step loop.
-    double run(int steps, std::vector<float> &av_vels) {
+    // the step loop.  accelerate = false: a later chunk of a run taken in
+    // chunks (the acceleration belongs to the first).
+    double run(int steps, std::vector<float> &av_vels, bool accelerate = true) {
         av_vels.assign(steps, 0.f);
         const auto t0 = std::chrono::steady_clock::now();
-        accelerate_first();
+        if (accelerate) accelerate_first();
         for (int t = 0; t < steps; ++t) {
             step(f_[cur_].data(), f_[1 - cur_].data());
             cur_ = 1 - cur_;

@@ -20,6 +20,12 @@
 //                           the non-equilibrium strain rate of
 //                           include/lbm_stress_hip.h on the host (lbm_runner
 //                           --stress; no reference counterpart)
+//   readTracers, tracerAdvance, tracerBlocked, writeTracers
+//                           the tracers of include/lbm_tracers_hip.h on the
+//                           host (lbm_runner --tracers; no reference
+//                           counterpart): the advance goes through
+//                           lbm_tracer_advance_ref, the per-point functions of
+//                           the kernels compiled for the host
 //   timedStep               main/include/GraphcoreUtils.hpp:130-138
 #pragma once
 
@@ -36,6 +42,7 @@
 #include <vector>
 
 #include "lbm_hip.h"
+#include "lbm_tracers_hip.h"
 
 namespace lbmhost {
 
@@ -469,6 +476,73 @@ inline bool writeBinnedState(const std::string &filename, const BinnedSums &b) {
             for (const auto &a : b.sum) fprintf(file, " %.12E", a[i]);
             fprintf(file, "\n");
         }
+    return fclose(file) == 0;
+}
+
+// ---- tracers and point probes (include/lbm_tracers_hip.h) ----
+
+struct Tracers {
+    std::vector<double> x, y;
+    std::vector<uint8_t> blocked;
+};
+
+// one `x y` per line (cell units); every point inside [0, nx) x [0, ny)
+inline std::optional<Tracers> readTracers(const std::string &filename, const Params &p) {
+    std::ifstream file(filename);
+    if (!file.is_open()) {
+        std::cerr << "Could not read tracers from " << filename << std::endl;
+        return std::nullopt;
+    }
+    Tracers t;
+    std::string line;
+    while (std::getline(file, line)) {
+        double x = 0.0, y = 0.0;
+        const int n = sscanf(line.c_str(), "%lf %lf", &x, &y);
+        if (n <= 0) continue;  // blank line
+        if (n != 2 || !(x >= 0.0 && x < (double)p.nx) || !(y >= 0.0 && y < (double)p.ny)) {
+            std::cerr << "Malformed tracer line (x y inside the grid expected): " << line << std::endl;
+            return std::nullopt;
+        }
+        t.x.push_back(x);
+        t.y.push_back(y);
+    }
+    if (t.x.empty()) {
+        std::cerr << "No tracer in " << filename << std::endl;
+        return std::nullopt;
+    }
+    return t;
+}
+
+// One advance by dt in the velocity field of the AoS cells: macroscopic()'s
+// u_x, u_y as planar arrays, then lbm_tracer_advance_ref.
+inline bool tracerAdvance(const Params &p, const Obstacles &o, const std::vector<float> &cells, Tracers &t, double dt,
+                          int scheme) {
+    std::vector<float> ux(p.nx * p.ny), uy(p.nx * p.ny);
+    for (size_t y = 0; y < p.ny; ++y)
+        for (size_t x = 0; x < p.nx; ++x) {
+            const Macro m = macroscopic(p, o, cells, x, y);
+            ux[x + y * p.nx] = m.ux;
+            uy[x + y * p.nx] = m.uy;
+        }
+    return lbm_tracer_advance_ref((int32_t)p.nx, (int32_t)p.ny, ux.data(), uy.data(), (int64_t)t.x.size(), t.x.data(),
+                                  t.y.data(), dt, scheme) == LBM_OK;
+}
+
+// the header's blocked flag: the nearest cell, floor(c + 0.5) taken to 0 at the extent, is an obstacle
+inline void tracerBlocked(const Obstacles &o, Tracers &t) {
+    auto nearest = [](double c, size_t n) {
+        const size_t i = (size_t)std::floor(c + 0.5);
+        return i == n ? (size_t)0 : i;
+    };
+    t.blocked.resize(t.x.size());
+    for (size_t i = 0; i < t.x.size(); ++i) t.blocked[i] = o.at(nearest(t.x[i], o.nx), nearest(t.y[i], o.ny)) ? 1 : 0;
+}
+
+// tracers.dat: `id x y blocked` per point, the positions in %.17g (they read back to the same doubles)
+inline bool writeTracers(const std::string &filename, const Tracers &t) {
+    FILE *file = fopen(filename.c_str(), "w");
+    if (!file) return false;
+    for (size_t i = 0; i < t.x.size(); ++i) fprintf(file, "%zu %.17g %.17g %d\n", i, t.x[i], t.y[i], (int)t.blocked[i]);
     return fclose(file) == 0;
 }
 

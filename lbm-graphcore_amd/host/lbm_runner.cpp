@@ -4,7 +4,7 @@
 //   lbm_runner --params P --obstacles O [-n N] [--device gpu|loopback|cpu] [-d] [--exe ignored]
 //              [--runs 5] [--kernel auto|resident|stream|step2|vec4|scalar|pipeline] [--spl S] [--out-dir DIR]
 //              [--tolerance] [--device-fields] [--forces] [--mean-every N] [--gradients] [--stress] [--binned BWxBH]
-//              [--json FILE]
+//              [--tracers FILE [--trace-every N] [--trace-scheme euler|heun]] [--json FILE]
 //
 // Flow (same program numbering as the reference):
 //   load params/obstacles -> initialise cells on host -> create engine
@@ -43,6 +43,14 @@
 // uxuy uyuy in %.12E (lbm_binned_hip.h) -- from lbm_store_binned and
 // lbm_bin_fluid_cells on the GPU, from lbmhost::binnedSums of the stored cells
 // with --device cpu.
+// --tracers FILE reads one seed point `x y` per line (cell units), runs the
+// first run in chunks of --trace-every steps (default 10; the chunking rule of
+// --mean-every) and moves the points after each chunk by dt = the steps of that
+// chunk with --trace-scheme (default heun), then writes tracers.dat after the
+// run: `id x y blocked` per point, the positions in %.17g (lbm_tracers_hip.h)
+// -- through lbm_tracer_begin / _advance / _store on the GPU, through
+// lbmhost::tracerAdvance (lbm_tracer_advance_ref over the stored cells'
+// velocities) with --device cpu.
 // --device loopback places all N sub-domains on GPU 0 (the emulator analogue
 // of --device ipumodel: exercises the multi-GPU halo path on one device).
 // --device cpu runs the same fused step on the host's cores (lbm_cpu.hpp:
@@ -57,6 +65,7 @@
 #include <iomanip>
 #include <iostream>
 #include <memory>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -67,6 +76,7 @@
 #include "lbm_gradients_hip.h"
 #include "lbm_host.hpp"
 #include "lbm_stress_hip.h"
+#include "lbm_tracers_hip.h"
 
 namespace {
 
@@ -100,6 +110,10 @@ void usage(const char *exe) {
               << "      --binned arg     BWxBH: also write binned_state.dat: per bin of BW x BH cells the fluid cells and\n"
               << "                       the fp64 sums of rho, rho u, u, |u| and the velocity products of the final state\n"
               << "                       (e.g. NXx1: the profile across the channel; 1xNY: the flux through each section)\n"
+              << "      --tracers arg    file of seed points, one `x y` per line in cell units: also write tracers.dat,\n"
+              << "                       the points moved with the flow (id x y blocked per point)\n"
+              << "      --trace-every arg  steps between two moves of the tracers (default: 10)\n"
+              << "      --trace-scheme arg euler or heun (default: heun)\n"
               << "      --out-dir arg    directory for av_vels.dat / final_state.dat (default: .)\n"
               << "      --graph-steps arg  replay the step loop as hipGraphs of 2*arg launches (0 = library default, <0 = off)\n"
               << "      --dump-partitioning arg  write the sub-domain decomposition as JSON\n"
@@ -121,7 +135,8 @@ std::string json_str(const std::string &v) {
 
 // --device cpu: the reference's program sequence on the host backend
 int run_cpu(const lbmhost::Params &params, const lbmhost::Obstacles &obstacles, const std::string &outDir, int runs,
-            bool forces, bool gradients, bool stress, int binW, int binH) {
+            bool forces, bool gradients, bool stress, int binW, int binH, lbmhost::Tracers *tracers, int traceEvery,
+            int traceScheme) {
     std::cout << "Running on the host CPU (" << lbmcpu::Engine::threads()
               << " threads; bitwise numerics: the reference's LastChance.cpp arithmetic)" << std::endl;
     auto cells = lbmhost::initialiseCells(params);
@@ -132,8 +147,25 @@ int run_cpu(const lbmhost::Params &params, const lbmhost::Obstacles &obstacles, 
                                              params.omega, obstacles.data);
     });
     lbmhost::timedStep("Running copy to device step", [&]() { e->load(cells); });
-    double total_compute_time =
-        lbmhost::timedStep("Running LBM", [&]() { e->run((int)params.maxIters, av_vels); });
+    double total_compute_time = lbmhost::timedStep("Running LBM", [&]() {
+        if (!tracers) {
+            e->run((int)params.maxIters, av_vels);
+            return;
+        }
+        // in chunks, the acceleration with the first; the points move after each chunk
+        std::vector<float> av;
+        for (int done = 0; done < (int)params.maxIters;) {
+            const int n = std::min(traceEvery, (int)params.maxIters - done);
+            e->run(n, av, done == 0);
+            av_vels.insert(av_vels.end(), av.begin(), av.end());
+            done += n;
+            e->store(cells);
+            if (!lbmhost::tracerAdvance(params, obstacles, cells, *tracers, (double)n, traceScheme)) {
+                std::cerr << "--tracers: lbm_tracer_advance_ref refused the points" << std::endl;
+                std::exit(EXIT_FAILURE);
+            }
+        }
+    });
     lbmhost::timedStep("Running copy to host step", [&]() { e->store(cells); });
     lbmhost::timedStep("Writing output files ", [&]() {
         lbmhost::writeAverageVelocities(outDir + "/av_vels.dat", av_vels);
@@ -160,6 +192,10 @@ int run_cpu(const lbmhost::Params &params, const lbmhost::Obstacles &obstacles, 
         if (binW > 0)
             lbmhost::writeBinnedState(outDir + "/binned_state.dat",
                                       lbmhost::binnedSums(params, obstacles, cells, (size_t)binW, (size_t)binH));
+        if (tracers) {
+            lbmhost::tracerBlocked(obstacles, *tracers);
+            lbmhost::writeTracers(outDir + "/tracers.dat", *tracers);
+        }
     });
     std::cout << "==done==" << std::endl;
     std::cout << "Total compute time was \t" << std::right << std::setw(12) << std::setprecision(5)
@@ -187,6 +223,8 @@ int run_cpu(const lbmhost::Params &params, const lbmhost::Obstacles &obstacles, 
 
 int main(int argc, char *argv[]) {
     std::string paramsFile, obstaclesFile, device = "gpu", exeFile, kernel = "auto", outDir = ".", dumpFile, jsonFile;
+    std::string tracersFile, traceSchemeName = "heun";
+    int traceEvery = 10;
     std::vector<std::string> gpuOnly;  // GPU-only options given on the command line
     int spl = 0;
     int numGpus = 1, runs = 5, graphSteps = 0, meanEvery = 0, binW = 0, binH = 0;
@@ -254,6 +292,17 @@ int main(int argc, char *argv[]) {
             meanEvery = std::atoi(v.c_str());
             if (meanEvery < 1) { usage(argv[0]); return EXIT_FAILURE; }
             gpuOnly.push_back(a);
+        } else if (a == "--tracers") {
+            if (!next(tracersFile)) { usage(argv[0]); return EXIT_FAILURE; }
+        } else if (a == "--trace-every") {
+            if (!next(v)) { usage(argv[0]); return EXIT_FAILURE; }
+            traceEvery = std::atoi(v.c_str());
+            if (traceEvery < 1) { usage(argv[0]); return EXIT_FAILURE; }
+        } else if (a == "--trace-scheme") {
+            if (!next(traceSchemeName) || (traceSchemeName != "euler" && traceSchemeName != "heun")) {
+                usage(argv[0]);
+                return EXIT_FAILURE;
+            }
         } else if (a == "--out-dir") {
             if (!next(outDir)) { usage(argv[0]); return EXIT_FAILURE; }
         } else if (a == "--graph-steps") {
@@ -295,6 +344,16 @@ int main(int argc, char *argv[]) {
             return EXIT_FAILURE;
         }
     }
+    const int traceScheme = traceSchemeName == "euler" ? LBM_TRACER_EULER : LBM_TRACER_HEUN;
+    std::optional<lbmhost::Tracers> tracers;
+    if (!tracersFile.empty()) {
+        if (meanEvery > 0) {
+            std::cerr << "--tracers and --mean-every each take the run in their own chunks: give one of them" << std::endl;
+            return EXIT_FAILURE;
+        }
+        tracers = lbmhost::readTracers(tracersFile, *params);
+        if (!tracers.has_value()) return EXIT_FAILURE;
+    }
     if (!dumpFile.empty()) {
         // partitioning.json in the layout of grids::serializeToJson
         // (StructuredGridUtils.hpp:135-158), one entry per GPU sub-domain;
@@ -331,7 +390,8 @@ int main(int argc, char *argv[]) {
             std::cerr << " (the host backend runs the reference arithmetic on one domain)" << std::endl;
             return EXIT_FAILURE;
         }
-        return run_cpu(*params, *obstacles, outDir, runs, forces, gradients, stress, binW, binH);
+        return run_cpu(*params, *obstacles, outDir, runs, forces, gradients, stress, binW, binH,
+                       tracers.has_value() ? &*tracers : nullptr, traceEvery, traceScheme);
     }
     const int ndev = lbm_device_count();
     if (ndev <= 0) {
@@ -397,12 +457,24 @@ int main(int argc, char *argv[]) {
                 done += n;
             }
         });
+    } else if (tracers.has_value()) {
+        total_compute_time += lbmhost::timedStep("Running LBM", [&]() {
+            lbmhost::check(lbm_tracer_begin(h, (int64_t)tracers->x.size(), tracers->x.data(), tracers->y.data()), h,
+                           "lbm_tracer_begin");
+            for (int done = 0; done < (int)params->maxIters;) {
+                const int n = std::min(traceEvery, (int)params->maxIters - done);
+                lbmhost::check(lbm_run_steps(h, n, done == 0), h, "lbm_run_steps");
+                lbmhost::check(lbm_store(h, nullptr, av_vels.data() + done, n), h, "lbm_store");
+                lbmhost::check(lbm_tracer_advance(h, (double)n, traceScheme), h, "lbm_tracer_advance");
+                done += n;
+            }
+        });
     } else {
         total_compute_time += lbmhost::timedStep("Running LBM", [&]() { lbmhost::check(lbm_run(h), h, "lbm_run"); });
     }
     std::vector<float> means[LBM_AVG_FIELDS];         // --mean-every: mean_state.dat's columns, planar
-    // --mean-every gathered av_vels per chunk: the last run's would overwrite them
-    float *const avOut = meanEvery > 0 ? nullptr : av_vels.data();
+    // --mean-every and --tracers gathered av_vels per chunk: the last run's would overwrite them
+    float *const avOut = (meanEvery > 0 || tracers.has_value()) ? nullptr : av_vels.data();
     std::vector<float> f_ux, f_uy, f_u, f_pressure;  // --device-fields: final_state.dat's columns, planar
     lbmhost::BodyForces bodyForces;                   // --forces: forces.dat
     std::vector<float> grads[LBM_GRAD_FIELDS];        // --gradients: gradient_state.dat's columns, planar
@@ -457,6 +529,12 @@ int main(int argc, char *argv[]) {
             lbmhost::check(lbm_store_binned(h, binW, binH, out), h, "lbm_store_binned");
             lbmhost::check(lbm_bin_fluid_cells(h, binW, binH, binned.fluid.data()), h, "lbm_bin_fluid_cells");
         }
+        if (tracers.has_value()) {
+            tracers->blocked.assign(tracers->x.size(), 0);
+            lbmhost::check(lbm_tracer_store(h, tracers->x.data(), tracers->y.data(), tracers->blocked.data()), h,
+                           "lbm_tracer_store");
+            lbmhost::check(lbm_tracer_end(h), h, "lbm_tracer_end");
+        }
         if (forces) {
             std::vector<int32_t> labels;
             const int32_t nbodies = lbmhost::labelBodies(*obstacles, labels);
@@ -479,6 +557,7 @@ int main(int argc, char *argv[]) {
             lbmhost::writeStressState(outDir + "/stress_state.dat", *params, *obstacles, strain,
                                       lbmhost::nearWall(*obstacles));
         if (binW > 0) lbmhost::writeBinnedState(outDir + "/binned_state.dat", binned);
+        if (tracers.has_value()) lbmhost::writeTracers(outDir + "/tracers.dat", *tracers);
         if (!means[0].empty()) lbmhost::writeMeanState(outDir + "/mean_state.dat", *params, *obstacles, means);
         lbmhost::writeAverageVelocities(outDir + "/av_vels.dat", av_vels);
         if (deviceFields)

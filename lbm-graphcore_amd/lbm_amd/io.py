@@ -19,6 +19,9 @@
 * binned_terms, binned_sums (+ ...3d), bin_reduce, binned_means
                         -- the binned sums of include/lbm_binned_hip.h: the per-cell terms in
                            numpy, math.fsum per bin (Engine.binned(), .profile_y(), .flux_x())
+* tracer_interp, tracer_advance, tracer_blocked (+ ...3d), tracer_wrap, read_tracers
+                        -- the tracers and point probes of include/lbm_tracers_hip.h in float64
+                           numpy (Engine.tracer_sample(), .tracers_advance(), .tracers())
 
 Error behaviour follows the reference: loaders return None (std::nullopt)
 and print the reference's message on stderr.  One deliberate strengthening:
@@ -654,6 +657,131 @@ def read_binned_state(filename: str, nbx: int, nby: int):
     out = {n: t[..., 3 + i].copy() for i, n in enumerate(BIN_FIELDS)}
     out["fluid"] = t[..., 2].astype(np.int64)
     return out
+
+
+# ---- Lagrangian tracers and point probes (include/lbm_tracers_hip.h) ----
+# float64 numpy restatements of the header's definition: every operation is one
+# numpy ufunc, so each is rounded once, in the header's order.
+
+TRACER_SCHEMES = {"euler": 0, "heun": 1}
+
+
+def tracer_wrap(v, n: int) -> np.ndarray:
+    """wrap(v, n): v - n * floor(v / n), and 0 wherever that is not in [0, n) (NaN, Inf)."""
+    v = np.asarray(v, np.float64)
+    n = np.float64(n)
+    with np.errstate(all="ignore"):
+        r = v - n * np.floor(v / n)
+    return np.where((r >= 0.0) & (r < n), r, np.float64(0.0))
+
+
+def _tracer_split(x, n: int):
+    x = np.asarray(x, np.float64)
+    i0 = np.floor(x).astype(np.int64)
+    t = x - i0.astype(np.float64)
+    i1 = np.where(i0 + 1 == n, 0, i0 + 1)
+    return i0, i1, t
+
+
+def _tracer_lerp(a, b, t):
+    with np.errstate(all="ignore"):
+        return a + t * (b - a)
+
+
+def tracer_interp(field, x, y) -> np.ndarray:
+    """The [ny][nx] field (fp32 values, widened to float64) interpolated bilinearly at the
+    points (x, y) in cell units, periodic: lbm_tracer_sample / lbm_tracer_sample_ref."""
+    f = np.asarray(field).astype(np.float64)
+    ny, nx = f.shape
+    i0, i1, tx = _tracer_split(x, nx)
+    j0, j1, ty = _tracer_split(y, ny)
+    lo = _tracer_lerp(f[j0, i0], f[j0, i1], tx)
+    hi = _tracer_lerp(f[j1, i0], f[j1, i1], tx)
+    return _tracer_lerp(lo, hi, ty)
+
+
+def tracer_interp3d(field, x, y, z) -> np.ndarray:
+    """The same for a [nz][ny][nx] field: along x first, then y, then z."""
+    f = np.asarray(field).astype(np.float64)
+    nz, ny, nx = f.shape
+    i0, i1, tx = _tracer_split(x, nx)
+    j0, j1, ty = _tracer_split(y, ny)
+    k0, k1, tz = _tracer_split(z, nz)
+    planes = []
+    for k in (k0, k1):
+        lo = _tracer_lerp(f[k, j0, i0], f[k, j0, i1], tx)
+        hi = _tracer_lerp(f[k, j1, i0], f[k, j1, i1], tx)
+        planes.append(_tracer_lerp(lo, hi, ty))
+    return _tracer_lerp(planes[0], planes[1], tz)
+
+
+def _tracer_scheme(scheme) -> int:
+    if isinstance(scheme, str):
+        if scheme not in TRACER_SCHEMES:
+            raise ValueError(f"scheme is one of {tuple(TRACER_SCHEMES)}; got {scheme!r}")
+        return TRACER_SCHEMES[scheme]
+    if int(scheme) not in TRACER_SCHEMES.values():
+        raise ValueError(f"scheme is one of {tuple(TRACER_SCHEMES)} (0, 1); got {scheme!r}")
+    return int(scheme)
+
+
+def _tracer_advance(fields, interp, pos, dt, scheme):
+    heun = _tracer_scheme(scheme) == 1
+    dt = np.float64(dt)
+    extent = np.shape(fields[0])[::-1]                    # (nx, ny[, nz])
+    pos = [np.asarray(c, np.float64) for c in pos]
+    with np.errstate(all="ignore"):
+        k1 = [interp(f, *pos) for f in fields]
+        if not heun:
+            return tuple(tracer_wrap(c + dt * k, n) for c, k, n in zip(pos, k1, extent))
+        mid = [tracer_wrap(c + dt * k, n) for c, k, n in zip(pos, k1, extent)]
+        k2 = [interp(f, *mid) for f in fields]
+        half = np.float64(0.5) * dt
+        return tuple(tracer_wrap(c + half * (a + b), n) for c, a, b, n in zip(pos, k1, k2, extent))
+
+
+def tracer_advance(ux, uy, x, y, dt, scheme="heun"):
+    """(x', y') after one advance by dt in the frozen [ny][nx] velocity fields ux, uy
+    (lbm_tracer_advance / lbm_tracer_advance_ref); scheme "euler" / "heun" or 0 / 1."""
+    return _tracer_advance((ux, uy), tracer_interp, (x, y), dt, scheme)
+
+
+def tracer_advance3d(ux, uy, uz, x, y, z, dt, scheme="heun"):
+    """(x', y', z') for [nz][ny][nx] fields (lbm3d_tracer_advance / _ref)."""
+    return _tracer_advance((ux, uy, uz), tracer_interp3d, (x, y, z), dt, scheme)
+
+
+def _tracer_nearest(x, n: int):
+    i = np.floor(np.asarray(x, np.float64) + np.float64(0.5)).astype(np.int64)
+    return np.where(i == n, 0, i)
+
+
+def tracer_blocked(obstacles, x, y) -> np.ndarray:
+    """uint8[n]: 1 where the nearest cell of the point is an obstacle (lbm_tracer_store)."""
+    o = np.asarray(obstacles)
+    ny, nx = o.shape
+    return (o[_tracer_nearest(y, ny), _tracer_nearest(x, nx)] != 0).astype(np.uint8)
+
+
+def tracer_blocked3d(obstacles, x, y, z) -> np.ndarray:
+    o = np.asarray(obstacles)
+    nz, ny, nx = o.shape
+    return (o[_tracer_nearest(z, nz), _tracer_nearest(y, ny), _tracer_nearest(x, nx)] != 0).astype(np.uint8)
+
+
+def read_tracers(filename: str):
+    """tracers.dat (`id x y blocked`, positions in %.17g) -> (x, y float64[n], blocked uint8[n]);
+    the positions through float() of the text: the runner's doubles, bit for bit."""
+    x, y, b = [], [], []
+    with open(filename, "r") as f:
+        for line in f:
+            t = line.split()
+            if not t:
+                continue
+            x.append(float(t[1]))
+            y.append(float(t[2]))
+            b.append(int(t[3]))
+    return np.asarray(x, np.float64), np.asarray(y, np.float64), np.asarray(b, np.uint8)
 
 
 def write_average_velocities(filename: str, av_vels) -> bool:

@@ -100,6 +100,20 @@ BIN_FIELDS3D = ("rho", "jx", "jy", "jz", "ux", "uy", "uz", "speed",
 # per lane); a chunk is at most BIN_CHUNK_ROWS planes.
 BIN_QUAD, BIN_WAVE_COLS, BIN_CHUNK_ROWS = 4, 256, 32
 BIN3D_WAVE_COLS = 64
+# every symbol include/lbm_tracers_hip.h declares (Lagrangian tracers and point probes; both engines)
+EXPORTED_TRACERS = [
+    "lbm_tracer_begin", "lbm_tracer_count", "lbm_tracer_advance", "lbm_tracer_sample", "lbm_tracer_store",
+    "lbm_tracer_end", "lbm_tracer_advance_ref", "lbm_tracer_sample_ref",
+    "lbm3d_tracer_begin", "lbm3d_tracer_count", "lbm3d_tracer_advance", "lbm3d_tracer_sample",
+    "lbm3d_tracer_store", "lbm3d_tracer_end", "lbm3d_tracer_advance_ref", "lbm3d_tracer_sample_ref",
+]
+TRACER_EULER, TRACER_HEUN = 0, 1          # LBM_TRACER_EULER / LBM_TRACER_HEUN
+TRACER_SCHEMES = {"euler": TRACER_EULER, "heun": TRACER_HEUN}
+TRACER_MAX_PARTS = 16                     # LBM_TRACER_MAX_PARTS
+TRACER_BLOCK = 256                        # lanes (= points) per block of the tracer kernels (csrc/lbm_tracers.hpp)
+# names of tracer_sample()'s arrays, in the argument order of lbm_tracer_sample / lbm3d_tracer_sample
+TRACER_FIELDS = ("ux", "uy", "pressure")
+TRACER_FIELDS3D = ("ux", "uy", "uz", "pressure")
 Q3 = 19
 
 
@@ -278,6 +292,24 @@ def load_library() -> ctypes.CDLL:
         "lbm_bin_fluid_cells": ([H, i32, i32, i64p], ctypes.c_int),
         "lbm3d_store_binned": ([H, i32, i32, i32, ctypes.POINTER(f64p)], ctypes.c_int),
         "lbm3d_bin_fluid_cells": ([H, i32, i32, i32, i64p], ctypes.c_int),
+        "lbm_tracer_begin": ([H, i64, f64p, f64p], ctypes.c_int),
+        "lbm_tracer_count": ([H, i64p], ctypes.c_int),
+        "lbm_tracer_advance": ([H, ctypes.c_double, i32], ctypes.c_int),
+        "lbm_tracer_sample": ([H, f64p, f64p, f64p], ctypes.c_int),
+        "lbm_tracer_store": ([H, f64p, f64p, u8p], ctypes.c_int),
+        "lbm_tracer_end": ([H], ctypes.c_int),
+        "lbm_tracer_advance_ref": ([i32, i32, f32p, f32p, i64, f64p, f64p, ctypes.c_double, i32], ctypes.c_int),
+        "lbm_tracer_sample_ref": ([i32, i32, f32p, f32p, f32p, i64, f64p, f64p, f64p, f64p, f64p], ctypes.c_int),
+        "lbm3d_tracer_begin": ([H, i64, f64p, f64p, f64p], ctypes.c_int),
+        "lbm3d_tracer_count": ([H, i64p], ctypes.c_int),
+        "lbm3d_tracer_advance": ([H, ctypes.c_double, i32], ctypes.c_int),
+        "lbm3d_tracer_sample": ([H, f64p, f64p, f64p, f64p], ctypes.c_int),
+        "lbm3d_tracer_store": ([H, f64p, f64p, f64p, u8p], ctypes.c_int),
+        "lbm3d_tracer_end": ([H], ctypes.c_int),
+        "lbm3d_tracer_advance_ref": ([i32, i32, i32, f32p, f32p, f32p, i64, f64p, f64p, f64p, ctypes.c_double, i32],
+                                     ctypes.c_int),
+        "lbm3d_tracer_sample_ref": ([i32, i32, i32, f32p, f32p, f32p, f32p, i64, f64p, f64p, f64p,
+                                     f64p, f64p, f64p, f64p], ctypes.c_int),
         "lbm3d_total_free_cells": ([H], i64),
         "lbm3d_local_slabs": ([H, i32p, i32p, i32, i32p], ctypes.c_int),
         "lbm3d_last_error": ([H], ctypes.c_char_p),
@@ -295,6 +327,83 @@ def load_library() -> ctypes.CDLL:
 
 def _f32(a: np.ndarray):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
+def _f64(a: np.ndarray):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+
+def _tracer_scheme(scheme) -> int:
+    if isinstance(scheme, str):
+        if scheme not in TRACER_SCHEMES:
+            raise ValueError(f"scheme is one of {tuple(TRACER_SCHEMES)}; got {scheme!r}")
+        return TRACER_SCHEMES[scheme]
+    return int(scheme)
+
+
+def _ref_fields(fields, dims):
+    """Planar fp32 fields of one shape (None allowed) for the *_ref entry points: (arrays, extents x first)."""
+    arrs = [None if f is None else np.ascontiguousarray(f, np.float32) for f in fields]
+    shapes = {a.shape for a in arrs if a is not None}
+    if len(shapes) != 1 or len(next(iter(shapes))) != dims:
+        raise ValueError(f"fields must be {dims}-D arrays of one shape")
+    return arrs, tuple(int(n) for n in next(iter(shapes))[::-1])
+
+
+def _ref_points(pos):
+    pts = [np.array(c, np.float64, ndmin=1) for c in pos]          # copies: advance_ref moves them in place
+    if len({c.shape for c in pts}) != 1 or pts[0].ndim != 1:
+        raise ValueError("positions must be 1-D arrays of one length")
+    return pts
+
+
+def tracer_advance_ref(ux, uy, x, y, dt, scheme="heun"):
+    """(x', y'): lbm_tracer_advance_ref -- the C++ per-point functions of the kernels, compiled
+    for the host, over planar float32[ny][nx] fields (no GPU).  lio.tracer_advance restates it."""
+    L = load_library()
+    (ux, uy), (nx, ny) = _ref_fields((ux, uy), 2)
+    x, y = _ref_points((x, y))
+    rc = L.lbm_tracer_advance_ref(nx, ny, _f32(ux), _f32(uy), x.size, _f64(x), _f64(y), float(dt),
+                                  _tracer_scheme(scheme))
+    if rc != LBM_OK:
+        raise LbmError(rc, "lbm_tracer_advance_ref: invalid argument")
+    return x, y
+
+
+def tracer_advance3d_ref(ux, uy, uz, x, y, z, dt, scheme="heun"):
+    """(x', y', z'): lbm3d_tracer_advance_ref over planar float32[nz][ny][nx] fields."""
+    L = load_library()
+    (ux, uy, uz), (nx, ny, nz) = _ref_fields((ux, uy, uz), 3)
+    x, y, z = _ref_points((x, y, z))
+    rc = L.lbm3d_tracer_advance_ref(nx, ny, nz, _f32(ux), _f32(uy), _f32(uz), x.size, _f64(x), _f64(y), _f64(z),
+                                    float(dt), _tracer_scheme(scheme))
+    if rc != LBM_OK:
+        raise LbmError(rc, "lbm3d_tracer_advance_ref: invalid argument")
+    return x, y, z
+
+
+def _sample_ref(fn, names, fields, pos):
+    dims = len(pos)
+    arrs, extent = _ref_fields(fields, dims)
+    pts = _ref_points(pos)
+    nan = np.float64(np.nan)
+    out = {n: np.full(pts[0].size, nan) for n, a in zip(names, arrs) if a is not None}
+    rc = fn(*extent, *[None if a is None else _f32(a) for a in arrs], pts[0].size, *[_f64(c) for c in pts],
+            *[_f64(out[n]) if n in out else None for n in names])
+    if rc != LBM_OK:
+        raise LbmError(rc, "tracer_sample_ref: invalid argument")
+    return out
+
+
+def tracer_sample_ref(ux, uy, pressure, x, y):
+    """{name: float64[n]} of the fields given (None: skipped) interpolated at (x, y):
+    lbm_tracer_sample_ref.  lio.tracer_interp restates it."""
+    return _sample_ref(load_library().lbm_tracer_sample_ref, TRACER_FIELDS, (ux, uy, pressure), (x, y))
+
+
+def tracer_sample3d_ref(ux, uy, uz, pressure, x, y, z):
+    """The D3Q19 twin: lbm3d_tracer_sample_ref."""
+    return _sample_ref(load_library().lbm3d_tracer_sample_ref, TRACER_FIELDS3D, (ux, uy, uz, pressure), (x, y, z))
 
 
 def partition(nx: int, ny: int, parts: int, grid_rows: int = 0, grid_cols: int = 0):
@@ -657,7 +766,113 @@ class _Binned:
         return out
 
 
-class Engine(_WallForces, _Averages, _Gradients, _Stress, _Binned):
+class _Tracers:
+    """Engine / Engine3D methods over include/lbm_tracers_hip.h; the class sets
+    _FORCE_PREFIX ("lbm_" / "lbm3d_"), _force_shape() and _TRACER_FIELDS."""
+
+    def _tracer_fn(self, name):
+        return getattr(self._L, self._FORCE_PREFIX + "tracer_" + name)
+
+    def _tracer_which(self, which):
+        names = self._TRACER_FIELDS
+        which = names if which is None else tuple(which)
+        bad = [n for n in which if n not in names]
+        if bad or len(set(which)) != len(which):
+            raise ValueError(f"sampled fields are a subset of {names}, each at most once; got {which}")
+        return which
+
+    def tracers_begin(self, x, y, z=None) -> None:
+        """Copy the seed points (cell units, 0 <= x < nx, ...; float64) to the device; a second
+        call replaces the set.  16 B (24 B) of device memory per point."""
+        dims = len(self._force_shape())
+        pos = (x, y) if dims == 2 else (x, y, z)
+        if (z is None) != (dims == 2):
+            raise ValueError(f"{dims} coordinate arrays expected")
+        pts = [np.ascontiguousarray(c, np.float64).reshape(-1) for c in pos]
+        if len({c.size for c in pts}) != 1:
+            raise ValueError("coordinate arrays must have one length")
+        self._check(self._tracer_fn("begin")(self._h, pts[0].size, *[_f64(c) for c in pts]))
+
+    @property
+    def tracer_count(self) -> int:
+        n = ctypes.c_int64()
+        self._check(self._tracer_fn("count")(self._h, ctypes.byref(n)))
+        return n.value
+
+    def tracers_advance(self, dt, scheme="heun") -> None:
+        """Move every point by dt lattice steps of the current lattice's velocity (one gather
+        kernel; nothing goes to the host): lio.tracer_advance[3d] of fields(), bit for bit."""
+        self._check(self._tracer_fn("advance")(self._h, float(dt), _tracer_scheme(scheme)))
+
+    def tracers(self):
+        """{"x", "y"[, "z"]: float64[n], "blocked": uint8[n]}: the current positions and whether
+        the nearest cell of each is an obstacle."""
+        n = self.tracer_count
+        names = ("x", "y", "z")[:len(self._force_shape())]
+        out = {c: np.full(n, np.nan) for c in names}
+        out["blocked"] = np.zeros(n, np.uint8)
+        self._check(self._tracer_fn("store")(self._h, *[_f64(out[c]) for c in names],
+                                             out["blocked"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+        return out
+
+    def tracer_sample(self, which=None):
+        """{name: float64[n]} of "ux", "uy"[, "uz"], "pressure" interpolated at the current
+        positions: lio.tracer_interp[3d] of fields(), bit for bit.  Default: every field."""
+        which = self._tracer_which(which)
+        n = self.tracer_count
+        out = {f: np.full(n, np.nan) for f in which}
+        self._check(self._tracer_fn("sample")(self._h, *[_f64(out[f]) if f in out else None
+                                                         for f in self._TRACER_FIELDS]))
+        return out
+
+    def tracers_end(self) -> None:
+        """Free the set (close() frees it too)."""
+        self._check(self._tracer_fn("end")(self._h))
+
+    def _traced_chunks(self, steps, every, accelerate_first, after):
+        steps, every = int(steps), int(every)
+        if steps < 0 or every < 1:
+            raise ValueError("steps >= 0 and every >= 1")
+        two_d = len(self._force_shape()) == 2
+        if accelerate_first and not two_d:
+            raise ValueError("accelerate_first applies to the D2Q9 engine only")
+        av, done = [], 0
+        while done < steps:
+            n = min(every, steps - done)
+            if two_d:
+                self.run_steps(n, accelerate_first and done == 0)
+                av.append(self.store(cells=False, n_av=n)[1].copy())
+            else:
+                self.run_steps(n)
+            done += n
+            after(n, done)
+        return np.concatenate(av) if av else np.zeros(0, np.float32)
+
+    def run_traced(self, steps: int, every: int, scheme="heun", accelerate_first: bool = False):
+        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and move the
+        tracers after each chunk by dt = the steps of that chunk (tracers_begin first), so a
+        shorter last chunk gets its own dt.  Returns the float32[steps] concatenation of the
+        chunks' average velocities (D3Q19: empty).  Chunking behaves as in run_averaged."""
+        scheme = _tracer_scheme(scheme)
+        return self._traced_chunks(steps, every, accelerate_first, lambda n, done: self.tracers_advance(n, scheme))
+
+    def probe_history(self, steps: int, every: int, which=None, accelerate_first: bool = False):
+        """The same chunks without moving the points: tracer_sample(which) after each chunk.
+        Returns {name: float64[samples, n]} and "step": the steps done at each sample."""
+        which = self._tracer_which(which)
+        samples, at = [], []
+
+        def after(n, done):
+            samples.append(self.tracer_sample(which))
+            at.append(done)
+        self._traced_chunks(steps, every, accelerate_first, after)
+        n = self.tracer_count
+        out = {f: (np.stack([s[f] for s in samples]) if samples else np.zeros((0, n))) for f in which}
+        out["step"] = np.asarray(at, np.int64)
+        return out
+
+
+class Engine(_WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
     """One lbm_handle: the HIP counterpart of the reference's poplar::Engine."""
 
     _FORCE_PREFIX = "lbm_"
@@ -665,6 +880,7 @@ class Engine(_WallForces, _Averages, _Gradients, _Stress, _Binned):
     _GRAD_FIELDS = GRAD_FIELDS
     _STRESS_FIELDS = STRESS_FIELDS
     _BIN_FIELDS = BIN_FIELDS
+    _TRACER_FIELDS = TRACER_FIELDS
 
     def strain_rate_local(self, which=None):
         """[{name: float32[h][w]}] per local rect (local_rects() order; lbm_store_stress_local)."""
@@ -974,7 +1190,7 @@ class Engine(_WallForces, _Averages, _Gradients, _Stress, _Binned):
             pass
 
 
-class Engine3D(_WallForces, _Averages, _Gradients, _Stress, _Binned):
+class Engine3D(_WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
     """One lbm3d_handle: the D3Q19 extension engine (include/lbm3d_hip.h)."""
 
     _FORCE_PREFIX = "lbm3d_"
@@ -982,6 +1198,7 @@ class Engine3D(_WallForces, _Averages, _Gradients, _Stress, _Binned):
     _GRAD_FIELDS = GRAD_FIELDS3D
     _STRESS_FIELDS = STRESS_FIELDS3D
     _BIN_FIELDS = BIN_FIELDS3D
+    _TRACER_FIELDS = TRACER_FIELDS3D
 
     def strain_rate_box(self, x0: int, y0: int, z0: int, nx: int, ny: int, nz: int, which=None):
         """{name: float32[nz][ny][nx]} of the cells [x0, x0+nx) x [y0, y0+ny) x [z0, z0+nz)
