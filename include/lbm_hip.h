@@ -330,6 +330,26 @@ int32_t lbm_steps_per_launch(lbm_handle *h);
  * one-step modes).  Lets a test prove which kernel advanced the lattice. */
 int lbm_run_stats(lbm_handle *h, int32_t *fused_launches, int32_t *one_step_launches);
 
+/* Read-only view of the stream kernel's work units (strip x segment, one wave
+ * each): per local sub-domain (lbm_local_rects order) the interior
+ * launch's units in unit index order, then the boundary launch's.  x0, y0, w,
+ * h: the cells the unit owns (writes), sub-domain-local, from the same helper
+ * the kernel's geometry uses; reads_obstacle: the per-unit flag the kernel
+ * reads, copied back from the device (1: the unit runs the copy with obstacle
+ * loads and rebound selects, 0: the select-free copy), -1 for every unit of a
+ * handle without flags (LBM_STREAM_UOBST=0: every unit runs the first copy).
+ * *n_out = number of units; at most max_out entries are written, and out may
+ * be NULL to ask for the count.  LBM_E_STATE when the handle's kernel is not
+ * the stream kernel, LBM_E_INVALID when h or n_out is NULL.  An additive part
+ * of the ABI (LBM_ABI_VERSION unchanged). */
+typedef struct lbm_stream_unit {
+    int32_t sub;            /* index in lbm_local_rects order */
+    int32_t boundary;       /* 0 interior launch, 1 boundary launch */
+    int32_t x0, y0, w, h;   /* owned cells, sub-domain-local */
+    int32_t reads_obstacle; /* the flag the kernel reads; -1 if the handle has none (LBM_STREAM_UOBST=0) */
+} lbm_stream_unit;
+int lbm_stream_units(lbm_handle *h, lbm_stream_unit *out, int32_t max_out, int32_t *n_out);
+
 /* Placement probe of lbm_create: the candidate lattice pair kept
  * (-1: no probe ran), how many pairs were timed, and (up to max_ms of) their
  * ms per launch. */

@@ -331,6 +331,39 @@ int lbm_run_stats(lbm_handle *h, int32_t *fused_launches, int32_t *one_step_laun
     return LBM_OK;
 }
 
+int lbm_stream_units(lbm_handle *h, lbm_stream_unit *out, int32_t max_out, int32_t *n_out) {
+    if (!h || !n_out) return LBM_E_INVALID;
+    if (lbm_kernel_in_use(h) != LBM_KERNEL_STREAM) {
+        h->err = "the handle's kernel is not the stream kernel";
+        return LBM_E_STATE;
+    }
+    return guarded(h, [&] {
+        int n = 0;
+        for (size_t i = 0; i < h->subs.size(); ++i) {
+            const Sub &s = h->subs[i];
+            const StreamArgs *launch[2] = {&s.a3_int[0], &s.a3_bnd[0]};
+            const int ni = std::max(0, launch[0]->total), nb = std::max(0, launch[1]->total);
+            // the flags the kernel reads, as build_args laid them out: [interior units | boundary units]
+            std::vector<uint8_t> fl((size_t)ni + nb);
+            if (s.uobst && !fl.empty()) {
+                h->set_device(s);
+                HIP_CHECK(hipMemcpy(fl.data(), s.uobst, fl.size(), hipMemcpyDeviceToHost));
+            }
+            for (int b = 0; b < 2; ++b) {
+                const StreamArgs &a = *launch[b];
+                for (int t = 0; t < std::max(0, a.total); ++t, ++n) {
+                    if (!out || n >= max_out) continue;
+                    const int r = rect_index(a.rect_begin, t);
+                    const StreamOwned o = stream_unit_owned(a.rect[r], t - a.rect_begin[r]);
+                    out[n] = lbm_stream_unit{(int32_t)i, b, o.xo0, o.yo0, o.xo1 - o.xo0, o.yo1 - o.yo0,
+                                             s.uobst ? (int32_t)fl[(size_t)(b ? ni : 0) + t] : -1};
+                }
+            }
+        }
+        *n_out = n;
+    });
+}
+
 int lbm_profile_summary(lbm_handle *h, lbm_kernel_time *out, int32_t max_out, int32_t *n_out) {
     if (!h || !n_out) return LBM_E_INVALID;
     if (!h->profile) {

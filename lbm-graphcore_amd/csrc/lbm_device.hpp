@@ -201,10 +201,7 @@ struct RectPos {
 // Every tile lies inside one rect, so the rect lookup stays scalar.
 template <int N>
 __device__ __forceinline__ int rect_of(const int (&rect_begin)[N], int t) {
-    int r = 0;
-#pragma unroll
-    for (int i = 1; i < N; ++i) r = (t >= rect_begin[i]) ? i : r;
-    return __builtin_amdgcn_readfirstlane(r);
+    return __builtin_amdgcn_readfirstlane(rect_index(rect_begin, t));
 }
 
 __device__ __forceinline__ RectPos locate(const Rect (&rect)[MAX_RECTS], const int (&rect_begin)[MAX_RECTS], int t,

@@ -28,6 +28,8 @@
 //       (The fused two-step kernel is the g = 2 case, historically "W2".)
 #pragma once
 
+#include <hip/hip_runtime.h>
+
 #include <cstdint>
 
 #include "lbm_views.hpp"
@@ -151,6 +153,37 @@ struct SRect {
     int nstrip, hs;     // strips across, rows per segment
     int ow;             // owned columns per strip
 };
+
+// Work unit (tile) t -> the rect that holds it: rect_begin lists each rect's
+// first unit, INT_MAX for unused slots.  The one statement of the lookup: the
+// kernels take it wave-uniform (lbm_device.hpp rect_of), lbm_stream_units on
+// the host.
+template <int N>
+__host__ __device__ __forceinline__ int rect_index(const int (&rect_begin)[N], int t) {
+    int r = 0;
+#pragma unroll
+    for (int i = 1; i < N; ++i) r = (t >= rect_begin[i]) ? i : r;
+    return r;
+}
+
+// Owned cells of a stream work unit: columns [xo0, xo1) x rows [yo0, yo1),
+// sub-domain-local.
+struct StreamOwned {
+    int xo0, xo1, yo0, yo1;
+};
+
+// Unit lt of rect R (units count strips first, then segments).  The one
+// statement of the owned rectangle: the kernel's geometry (lbm_stream2.hip
+// stream2d_geo) and lbm_stream_units both call it.
+__host__ __device__ __forceinline__ StreamOwned stream_unit_owned(const SRect &R, int lt) {
+    const int seg = lt / R.nstrip, strip = lt - seg * R.nstrip;
+    StreamOwned o;
+    o.xo0 = R.x0 + strip * R.ow;               // first owned column
+    o.xo1 = min(o.xo0 + R.ow, R.x0 + R.w);     // past the last owned column
+    o.yo0 = R.y0 + seg * R.hs;
+    o.yo1 = min(o.yo0 + R.hs, R.y0 + R.h);
+    return o;
+}
 
 struct StreamArgs {
     const float *fin;

@@ -324,18 +324,16 @@ template <int S>
 __device__ __forceinline__ Stream2Geo stream2d_geo(const StreamArgs &a, int t, int lane) {
     const int r = rect_of(a.rect_begin, t);
     const SRect R = a.rect[r];
-    const int lt = t - a.rect_begin[r];
-    const int seg = lt / R.nstrip, strip = lt - seg * R.nstrip;
-    const int xo0 = R.x0 + strip * R.ow;             // first owned column
-    const int xo1 = min(xo0 + R.ow, R.x0 + R.w);     // past the last owned column
+    const StreamOwned o = stream_unit_owned(R, t - a.rect_begin[r]);
+    const int xo0 = o.xo0, xo1 = o.xo1;
     const int base = (xo0 - S) & ~1;                 // even: float2-aligned
     Stream2Geo g;
     g.xa = base + 2 * lane;
     g.xb = g.xa + 1;
     g.owna = g.xa >= xo0 && g.xa < xo1;
     g.ownb = g.xb >= xo0 && g.xb < xo1;
-    g.yo0 = R.y0 + seg * R.hs;
-    g.yo1 = min(g.yo0 + R.hs, R.y0 + R.h);
+    g.yo0 = o.yo0;
+    g.yo1 = o.yo1;
     const int xca = min(g.xa, (a.xmax - 1) & ~1);
     g.P = a.plane;
     g.pitch = a.pitch;

@@ -39,7 +39,7 @@ EXPORTED = [
     "lbm_store_fields", "lbm_store_fields_local", "lbm_field_stats",
     "lbm_last_run_seconds",
     "lbm_total_free_cells", "lbm_local_rects", "lbm_kernel_in_use", "lbm_steps_per_launch",
-    "lbm_run_stats", "lbm_profile_summary", "lbm_profile_reset", "lbm_placement_probe", "lbm_numerics", "lbm_nonfinite_count", "lbm_source_hash",
+    "lbm_run_stats", "lbm_stream_units", "lbm_profile_summary", "lbm_profile_reset", "lbm_placement_probe", "lbm_numerics", "lbm_nonfinite_count", "lbm_source_hash",
     "lbm_last_error", "lbm_destroy",
 ]
 # every symbol include/lbm3d_hip.h declares (D3Q19 extension)
@@ -176,6 +176,13 @@ class KernelTime(ctypes.Structure):
                 ("min_ms", ctypes.c_double), ("max_ms", ctypes.c_double)]
 
 
+class StreamUnit(ctypes.Structure):
+    """lbm_stream_unit (include/lbm_hip.h): one work unit of the stream kernel."""
+    _fields_ = [("sub", ctypes.c_int32), ("boundary", ctypes.c_int32), ("x0", ctypes.c_int32),
+                ("y0", ctypes.c_int32), ("w", ctypes.c_int32), ("h", ctypes.c_int32),
+                ("reads_obstacle", ctypes.c_int32)]
+
+
 class Xfer(ctypes.Structure):
     """lbm_xfer (include/lbm_hip.h): one post of a halo exchange."""
     _fields_ = [("op", ctypes.c_int32), ("dir", ctypes.c_int32), ("peer", ctypes.c_int32),
@@ -240,6 +247,7 @@ def load_library() -> ctypes.CDLL:
         "lbm_kernel_in_use": ([H], i32),
         "lbm_steps_per_launch": ([H], i32),
         "lbm_run_stats": ([H, i32p, i32p], ctypes.c_int),
+        "lbm_stream_units": ([H, ctypes.POINTER(StreamUnit), i32, i32p], ctypes.c_int),
         "lbm_profile_summary": ([H, ctypes.POINTER(KernelTime), i32, i32p], ctypes.c_int),
         "lbm_profile_reset": ([H], ctypes.c_int),
         "lbm_placement_probe": ([H, i32p, i32p, f32p, i32], ctypes.c_int),
@@ -1142,6 +1150,17 @@ class Engine(_WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
         a, b = ctypes.c_int32(), ctypes.c_int32()
         self._check(self._L.lbm_run_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    def stream_units(self):
+        """[(sub, boundary, x0, y0, w, h, reads_obstacle)] per work unit of the stream
+        kernel (lbm_stream_units): per local rect the interior launch's units, then
+        the boundary launch's; x0, y0, w, h are the owned cells, sub-domain-local;
+        reads_obstacle is the flag the kernel reads (-1: the handle keeps none)."""
+        n = ctypes.c_int32()
+        self._check(self._L.lbm_stream_units(self._h, None, 0, ctypes.byref(n)))
+        buf = (StreamUnit * max(n.value, 1))()
+        self._check(self._L.lbm_stream_units(self._h, buf, n.value, ctypes.byref(n)))
+        return [(u.sub, u.boundary, u.x0, u.y0, u.w, u.h, u.reads_obstacle) for u in buf[:n.value]]
 
     def profile_summary(self):
         """[{name, launches, total_ms, min_ms, max_ms}] per launch class (LBM_FLAG_PROFILE handles)."""
