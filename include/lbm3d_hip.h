@@ -6,8 +6,10 @@
  * The reference has NO 3-D code: this is the stretch extension of its D2Q9
  * hot path, kept as close to it as a third dimension allows, and its parity
  * is pinned only against our own CPU restatement (oracle/lbm_oracle3d.c,
- * bitwise) plus physics checks (mass conservation, Poiseuille profile) --
- * "parity unpinned" with respect to the reference.
+ * bitwise) plus physics checks (mass conservation, Poiseuille profile) and a
+ * float64 model written from the definition of D3Q19 that the restatement is
+ * held to (tests/test_d3q19_model.py) -- "parity unpinned" with respect to
+ * the reference.
  *
  * Model (mirrors main/LastChance.cpp:192-266 in 3-D):
  *   * pull streaming, periodic in x, y and z; obstacle cells bounce back
@@ -97,6 +99,26 @@ int lbm3d_store(lbm3d_handle *h, float *cells_aos, float *av_vels, int32_t n_av)
 
 /* Device-event seconds of the last lbm3d_run_steps. */
 int lbm3d_last_run_seconds(lbm3d_handle *h, double *seconds);
+
+/* What the last lbm3d_run_steps ran (all 0 before the first run; a refused
+ * run leaves them): three-step passes, two-step passes and one-step launches
+ * -- one count per pass / step of the whole domain, however many slabs and
+ * kernel launches it took; 3 three + 2 two + one = the steps asked for.
+ * *pair_kernel = 1 when this handle's one-step launches use the column-pair
+ * kernel (step3d_pair: nx even), 0 for the one-cell kernel (step3d).  Passes
+ * are not used, whatever was asked for, by z slabs thinner than 2n planes
+ * (n = 2, 3) or, for n = 3, when a plane's byte offsets reach 2^31.  Any
+ * pointer may be NULL. */
+int lbm3d_run_stats(lbm3d_handle *h, int32_t *three_step_passes, int32_t *two_step_passes,
+                    int32_t *one_step_launches, int32_t *pair_kernel);
+
+/* 0: bitwise (every kernel of this handle equals the CPU restatement);
+ * 1: tolerance (LBM_FLAG_TOLERANCE and the handle runs two- / three-step
+ * passes: they use the reciprocal collision).  One-step launches are bitwise
+ * in both modes, so a tolerance handle that cannot run passes reports 0, and
+ * the remainder steps of a tolerance run add no error of their own.  -1 for a
+ * NULL handle. */
+int32_t lbm3d_numerics(lbm3d_handle *h);
 
 /* Fluid (non-obstacle) cells of the full domain. */
 int64_t lbm3d_total_free_cells(lbm3d_handle *h);

@@ -216,6 +216,21 @@ int lbm3d_last_run_seconds(lbm3d_handle *h, double *seconds) {
     return LBM_OK;
 }
 
+int lbm3d_run_stats(lbm3d_handle *h, int32_t *three_step_passes, int32_t *two_step_passes,
+                    int32_t *one_step_launches, int32_t *pair_kernel) {
+    if (!h) return LBM_E_INVALID;
+    if (three_step_passes) *three_step_passes = h->run_three;
+    if (two_step_passes) *two_step_passes = h->run_two;
+    if (one_step_launches) *one_step_launches = h->run_one;
+    if (pair_kernel) *pair_kernel = h->pair ? 1 : 0;
+    return LBM_OK;
+}
+
+int32_t lbm3d_numerics(lbm3d_handle *h) {
+    if (!h) return -1;
+    return h->tolerance && h->use_two() ? 1 : 0;  // only the passes run cell3dt
+}
+
 int64_t lbm3d_total_free_cells(lbm3d_handle *h) { return h ? h->free_cells : -1; }
 
 int lbm3d_local_slabs(lbm3d_handle *h, int32_t *z0, int32_t *nz, int32_t max_slabs, int32_t *n_out) {

@@ -585,6 +585,7 @@ void lbm3d_handle::run_steps(int steps) {
         HIP_CHECK(hipEventRecord(s.ev_x, s.s_comp));
     }
     int t = 0;
+    run_three = run_two = run_one = 0;
     if (use_two() && steps >= 2) {
         if (multi()) {  // two- / three-plane ghosts of the current lattice (a one-step launch leaves only its five speeds)
             for (auto &s : slabs) {
@@ -594,10 +595,10 @@ void lbm3d_handle::run_steps(int steps) {
             post_exchange(slabs[0].cur, use_three() && steps >= 3 ? 3 : 2, false);
         }
         if (use_three())
-            for (; t + 3 <= steps; t += 3) step_pass(3, t);
-        for (; t + 2 <= steps; t += 2) step_pass(2, t);
+            for (; t + 3 <= steps; t += 3, ++run_three) step_pass(3, t);
+        for (; t + 2 <= steps; t += 2, ++run_two) step_pass(2, t);
     }
-    for (; t < steps; ++t) step_once(t);
+    for (; t < steps; ++t, ++run_one) step_once(t);
     for (auto &s : slabs) {
         HIP_CHECK(hipSetDevice(s.dev));
         HIP_CHECK(hipStreamWaitEvent(s.s_comp, s.ev_x, 0));

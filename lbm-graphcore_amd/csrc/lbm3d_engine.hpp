@@ -182,6 +182,7 @@ struct lbm3d_handle {
     int64_t free_cells = 0;
     bool loaded = false;
     int last_steps = 0;
+    int run_three = 0, run_two = 0, run_one = 0;  // passes / one-step launches of the last run_steps (lbm3d_run_stats)
     double last_seconds = 0.0;
     hipEvent_t t0 = nullptr, t1 = nullptr;
     std::string err;

@@ -46,6 +46,7 @@ EXPORTED = [
 EXPORTED3D = [
     "lbm3d_create", "lbm3d_init_equilibrium", "lbm3d_load_cells", "lbm3d_run_steps", "lbm3d_store",
     "lbm3d_last_run_seconds", "lbm3d_total_free_cells", "lbm3d_local_slabs", "lbm3d_exchange_schedule",
+    "lbm3d_run_stats", "lbm3d_numerics",
     "lbm3d_last_error", "lbm3d_destroy",
 ]
 # every symbol include/lbm3d_fields_hip.h declares (D3Q19 fields, box extracts, stats)
@@ -272,6 +273,8 @@ def load_library() -> ctypes.CDLL:
         "lbm3d_set_bodies": ([H, i32p, i32], ctypes.c_int),
         "lbm3d_body_forces": ([H, f64p, f64p, f64p, i64p, i32], ctypes.c_int),
         "lbm3d_last_run_seconds": ([H, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+        "lbm3d_run_stats": ([H, i32p, i32p, i32p, i32p], ctypes.c_int),
+        "lbm3d_numerics": ([H], i32),
         "lbm_avg_begin": ([H, i32], ctypes.c_int),
         "lbm_avg_sample": ([H], ctypes.c_int),
         "lbm_avg_samples": ([H, i64p], ctypes.c_int),
@@ -1373,6 +1376,20 @@ class Engine3D(_WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
         s = ctypes.c_double()
         self._check(self._L.lbm3d_last_run_seconds(self._h, ctypes.byref(s)))
         return s.value
+
+    def run_stats(self):
+        """(three-step passes, two-step passes, one-step launches, pair kernel) of the last
+        run_steps (lbm3d_run_stats): one count per pass / step of the whole domain; the last
+        entry is 1 when one-step launches use the column-pair kernel, 0 for the one-cell one."""
+        v = [ctypes.c_int32() for _ in range(4)]
+        self._check(self._L.lbm3d_run_stats(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def numerics(self) -> str:
+        """'tolerance' when this handle's two- / three-step passes run the reciprocal
+        collision (FLAG_TOLERANCE and passes in use), else 'bitwise'.  One-step launches
+        are bitwise in both modes."""
+        return "tolerance" if int(self._L.lbm3d_numerics(self._h)) == 1 else "bitwise"
 
     def total_free_cells(self) -> int:
         return int(self._L.lbm3d_total_free_cells(self._h))

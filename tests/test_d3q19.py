@@ -4,7 +4,8 @@ with respect to the reference, which has no 3-D code.
 What pins it instead:
 * CPU: the restatement (oracle/lbm_oracle3d.c) reproduces the analytic
   Poiseuille profile between bounce-back wall planes, conserves mass, and
-  keeps a z-mirror-symmetric state symmetric;
+  keeps a z-mirror-symmetric state symmetric; tests/test_d3q19_model.py holds
+  it to a float64 model built from the definition of D3Q19 alone;
 * GPU (through the C ABI, include/lbm3d_hip.h): the HIP lattice is BITWISE
   equal to the restatement -- one slab, z slabs on one GPU (device-copy
   halos), and the RCCL exchange path (one rank sending its faces to itself).
@@ -87,12 +88,27 @@ def _problem(nx, ny, nz, seed, accel=0.002):
     return p, obst, c0
 
 
-def _gpu3d(native, p, obst, c0, steps, **kw):
+def _forms(steps, nx, pair=True, two=True, three=True):
+    """run_stats() of `steps` steps: (three-step passes, two-step passes, one-step
+    launches, pair kernel) for an engine whose knobs and slabs allow the given pass
+    forms (three-step passes need two-step ones; the pair kernel needs an even nx)."""
+    n3 = steps // 3 if two and three else 0
+    n2 = (steps - 3 * n3) // 2 if two else 0
+    return n3, n2, steps - 3 * n3 - 2 * n2, int(pair and nx % 2 == 0)
+
+
+def _gpu3d(native, p, obst, c0, steps, expect=None, numerics=None, **kw):
+    """Load, run, store; expect = the run_stats() the run must report, numerics = the
+    numerics() the handle must report (neither is checked when None)."""
     with native.Engine3D(p, obst, **kw) as e:
         e.load_cells(c0)
         e.run_steps(steps)
         cells, av = e.store(n_av=steps)
         assert e.total_free_cells() == int((obst == 0).sum())
+        if expect is not None:
+            assert e.run_stats() == tuple(expect), (e.run_stats(), expect)
+        if numerics is not None:
+            assert e.numerics() == numerics
     return cells, av
 
 
@@ -112,7 +128,9 @@ def test_d3q19_bitwise_single_slab(gpu_lib, nx, ny, nz, pair, two, seg, monkeypa
     monkeypatch.setenv("LBM3D_SEG", seg)
     p, obst, c0 = _problem(nx, ny, nz, nx + ny + nz)
     ref, ref_av = oracle.run3d(p, obst, 9, c0)
-    cells, av = _gpu3d(gpu_lib, p, obst, c0, 9, devices=[0])
+    # four two-step passes + one launch, or nine launches; the kernel the knob and nx select
+    cells, av = _gpu3d(gpu_lib, p, obst, c0, 9, devices=[0], numerics="bitwise",
+                       expect=_forms(9, nx, pair=pair == "1", two=two == "1", three=False))
     assert np.array_equal(cells, ref)
     np.testing.assert_allclose(av, ref_av, rtol=1e-5)
 
@@ -220,15 +238,20 @@ def test_d3q19_slabs_two_step_bitwise(gpu_lib, parts, seg, steps, monkeypatch):
     """Two steps per pass on z slabs (BASELINE config 5's 8-slab form): each pass
     computes the two boundary plane pairs first, exchanges them (all 19 speeds of
     two planes each way) and then the interior; odd step counts end with a
-    one-step launch.  Ragged slabs of 5..20 planes, z segments of 1..64 planes."""
+    one-step launch.  Ragged slabs of 5..20 planes, z segments of 1..64 planes.
+    The three-step pass (the default where every slab has 6 planes: all but the
+    8-slab case) is switched off, so that every case runs the pass this test is
+    about; test_d3q19_slabs_three_step_bitwise covers the other."""
     monkeypatch.setenv("LBM3D_SEG", seg)
+    monkeypatch.setenv("LBM3D_THREE", "0")
     p, obst, c0 = _problem(22, 9, 40, 100 + parts)
     ref, ref_av = oracle.run3d(p, obst, steps, c0)
-    cells, av = _gpu3d(gpu_lib, p, obst, c0, steps, parts=parts, devices=[0])
+    cells, av = _gpu3d(gpu_lib, p, obst, c0, steps, parts=parts, devices=[0],
+                       expect=_forms(steps, p.nx, three=False))
     assert np.array_equal(cells, ref)
     np.testing.assert_allclose(av, ref_av, rtol=1e-5)
     monkeypatch.setenv("LBM3D_TWO", "0")  # the one-step slab path gives the same lattice
-    cells1, _ = _gpu3d(gpu_lib, p, obst, c0, steps, parts=parts, devices=[0])
+    cells1, _ = _gpu3d(gpu_lib, p, obst, c0, steps, parts=parts, devices=[0], expect=_forms(steps, p.nx, two=False))
     assert np.array_equal(cells1, ref)
 
 
@@ -284,7 +307,8 @@ def test_d3q19_three_step_bitwise(gpu_lib, nx, ny, nz, seg3, skip3, monkeypatch)
     p, obst, c0 = _problem(nx, ny, nz, 3 * nx + ny + nz)
     for steps in (10, 8):
         ref, ref_av = oracle.run3d(p, obst, steps, c0)
-        cells, av = _gpu3d(gpu_lib, p, obst, c0, steps, devices=[0])
+        # 10 steps: (3, 0, 1), 8 steps: (2, 1, 0)
+        cells, av = _gpu3d(gpu_lib, p, obst, c0, steps, devices=[0], expect=_forms(steps, nx), numerics="bitwise")
         assert np.array_equal(cells, ref), steps
         np.testing.assert_allclose(av, ref_av, rtol=1e-5)
 
@@ -308,11 +332,13 @@ def test_d3q19_three_step_reruns_and_tolerance(gpu_lib, monkeypatch):
     # 6 steps: two three-step passes / three two-step passes (a one-step
     # launch would use the bitwise pair kernel in both modes)
     ref6, _ = oracle.run3d(p, obst, 6, c0)
-    tol3, _ = _gpu3d(gpu_lib, p, obst, c0, 6, devices=[0], flags=gpu_lib.FLAG_TOLERANCE)
+    tol3, _ = _gpu3d(gpu_lib, p, obst, c0, 6, devices=[0], flags=gpu_lib.FLAG_TOLERANCE, expect=(2, 0, 0, 1),
+                     numerics="tolerance")
     dev = float(np.max(np.abs(tol3.astype(np.float64) - ref6) / np.maximum(np.abs(ref6), 1e-30)))
     assert dev < 2e-5, dev
     monkeypatch.setenv("LBM3D_THREE", "0")
-    tol2, _ = _gpu3d(gpu_lib, p, obst, c0, 6, parts=3, devices=[0], flags=gpu_lib.FLAG_TOLERANCE)
+    tol2, _ = _gpu3d(gpu_lib, p, obst, c0, 6, parts=3, devices=[0], flags=gpu_lib.FLAG_TOLERANCE, expect=(0, 3, 0, 1),
+                     numerics="tolerance")
     assert np.array_equal(tol3, tol2)
 
 
@@ -327,9 +353,12 @@ def test_d3q19_slabs_three_step_bitwise(gpu_lib, parts, seg3, monkeypatch):
     monkeypatch.setenv("LBM3D_THREE", "1")
     monkeypatch.setenv("LBM3D_SEG3", seg3)
     p, obst, c0 = _problem(22, 9, 40, 200 + parts)
+    three = p.nz // parts >= 6  # the thinnest slab has floor(nz / parts) planes; a three-step pass needs 6
+    assert three == (parts != 7)
     for steps in (10, 8):
         ref, ref_av = oracle.run3d(p, obst, steps, c0)
-        cells, av = _gpu3d(gpu_lib, p, obst, c0, steps, parts=parts, devices=[0])
+        cells, av = _gpu3d(gpu_lib, p, obst, c0, steps, parts=parts, devices=[0],
+                           expect=_forms(steps, p.nx, three=three))
         assert np.array_equal(cells, ref), steps
         np.testing.assert_allclose(av, ref_av, rtol=1e-5)
 
@@ -378,8 +407,9 @@ def test_d3q19_tolerance_vs_oracle(gpu_lib, parts):
     equal to one slab)."""
     p, obst, c0 = _problem(70, 31, 24, 99)
     ref, ref_av = oracle.run3d(p, obst, 8, c0)
-    one, _ = _gpu3d(gpu_lib, p, obst, c0, 8, devices=[0], flags=gpu_lib.FLAG_TOLERANCE)
-    cells, av = _gpu3d(gpu_lib, p, obst, c0, 8, parts=parts, devices=[0], flags=gpu_lib.FLAG_TOLERANCE)
+    one, _ = _gpu3d(gpu_lib, p, obst, c0, 8, devices=[0], flags=gpu_lib.FLAG_TOLERANCE, numerics="tolerance")
+    cells, av = _gpu3d(gpu_lib, p, obst, c0, 8, parts=parts, devices=[0], flags=gpu_lib.FLAG_TOLERANCE,
+                       numerics="tolerance", expect=(2, 1, 0, 1))  # slabs of 8 planes: three-step passes in both
     dev = float(np.max(np.abs(cells.astype(np.float64) - ref) / np.maximum(np.abs(ref), 1e-30)))
     assert dev < 2e-5, dev
     assert not np.array_equal(cells, ref)  # the flag really selects the other collision
@@ -421,7 +451,8 @@ def test_d3q19_tolerance_long_run(gpu_lib, three, monkeypatch):
     steps = 3000
     p, obst, c0 = _problem(70, 31, 24, 4242)
     ref, ref_av = oracle.run3d(p, obst, steps, c0)
-    cells, av = _gpu3d(gpu_lib, p, obst, c0, steps, devices=[0], flags=gpu_lib.FLAG_TOLERANCE)
+    cells, av = _gpu3d(gpu_lib, p, obst, c0, steps, devices=[0], flags=gpu_lib.FLAG_TOLERANCE, numerics="tolerance",
+                       expect=_forms(steps, p.nx, three=three == "1"))
     dev = float(np.max(np.abs(cells.astype(np.float64) - ref) / np.maximum(np.abs(ref), 1e-30)))
     dav = float(np.max(np.abs(av.astype(np.float64) - ref_av) / np.abs(ref_av)))
     print(f"D3Q19 tolerance {steps} steps (three={three}): populations {dev:.3e}, av_vels {dav:.3e}")

@@ -1,7 +1,7 @@
 """Host side of the D3Q19 device-fields path (CPU only).
 
 * include/lbm3d_fields_hip.h declares exactly native.EXPORTED3D_FIELDS, the
-  library exports them, lbm3d_hip.h keeps its 11 symbols, and each new entry
+  library exports them, lbm3d_hip.h keeps its 13 symbols, and each new entry
   point refuses a NULL handle.
 * The definition of the fields (lio.macroscopic3d, the numpy restatement the
   GPU tests compare against) is pinned to the oracle bit for bit: the
@@ -50,7 +50,7 @@ def test_fields_header_and_exports():
         assert re.search(rf"\bT {s}\b", out), s
     # the engine's own header is unchanged: the new names are no part of it
     base = header_symbols("lbm3d_hip.h", "lbm3d_")
-    assert len(base) == 11 and sorted(native.EXPORTED3D) == base
+    assert len(base) == 13 and sorted(native.EXPORTED3D) == base
     assert not set(base) & set(syms)
     assert native.FIELDS3D == ("ux", "uy", "uz", "speed", "pressure")
 
