@@ -220,13 +220,14 @@ def load_library() -> ctypes.CDLL:
     u8p = ctypes.POINTER(ctypes.c_uint8)
     i32p = ctypes.POINTER(ctypes.c_int32)
     f64p, i64p = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
+    f32pp, f64pp = ctypes.POINTER(f32p), ctypes.POINTER(f64p)
     sig = {
+        # include/lbm_hip.h (lbm_source_hash is declared above)
         "lbm_abi_version": ([], i32),
         "lbm_partition": ([i32, i32, i32, i32, i32, i32p, i32p, ctypes.POINTER(Rect)], ctypes.c_int),
         "lbm_halo_plan": ([i32p], ctypes.c_int),
         "lbm_exchange_schedule": ([i32, i32, i32, i32, i32, i32, i32, i32, i32, ctypes.POINTER(Xfer), i32, i32p],
                                   ctypes.c_int),
-        "lbm3d_exchange_schedule": ([i32, i32, i32, i32, i32, i32, ctypes.POINTER(Xfer), i32, i32p], ctypes.c_int),
         "lbm_device_count": ([], i32),
         "lbm_rccl_unique_id": ([u8p], ctypes.c_int),
         "lbm_create": ([ctypes.POINTER(Params), u8p, i32, ctypes.POINTER(H)], ctypes.c_int),
@@ -241,8 +242,8 @@ def load_library() -> ctypes.CDLL:
         "lbm_local_cells": ([H], i64),
         "lbm_store_fields": ([H, f32p, f32p, f32p, f32p], ctypes.c_int),
         "lbm_store_fields_local": ([H, f32p, f32p, f32p, f32p], ctypes.c_int),
-        "lbm_field_stats": ([H, ctypes.POINTER(ctypes.c_double), f32p], ctypes.c_int),
-        "lbm_last_run_seconds": ([H, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+        "lbm_field_stats": ([H, f64p, f32p], ctypes.c_int),
+        "lbm_last_run_seconds": ([H, f64p], ctypes.c_int),
         "lbm_total_free_cells": ([H], i64),
         "lbm_local_rects": ([H, ctypes.POINTER(Rect), i32, i32p], ctypes.c_int),
         "lbm_kernel_in_use": ([H], i32),
@@ -253,17 +254,28 @@ def load_library() -> ctypes.CDLL:
         "lbm_profile_reset": ([H], ctypes.c_int),
         "lbm_placement_probe": ([H, i32p, i32p, f32p, i32], ctypes.c_int),
         "lbm_numerics": ([H], i32),
-        "lbm_nonfinite_count": ([H, ctypes.POINTER(i64)], ctypes.c_int),
+        "lbm_nonfinite_count": ([H, i64p], ctypes.c_int),
         "lbm_last_error": ([H], ctypes.c_char_p),
         "lbm_destroy": ([H], None),
+        # include/lbm3d_hip.h
         "lbm3d_create": ([ctypes.POINTER(Params3D), u8p, ctypes.POINTER(Config), ctypes.POINTER(H)], ctypes.c_int),
         "lbm3d_init_equilibrium": ([H], ctypes.c_int),
         "lbm3d_load_cells": ([H, f32p], ctypes.c_int),
         "lbm3d_run_steps": ([H, i32], ctypes.c_int),
         "lbm3d_store": ([H, f32p, f32p, i32], ctypes.c_int),
+        "lbm3d_last_run_seconds": ([H, f64p], ctypes.c_int),
+        "lbm3d_total_free_cells": ([H], i64),
+        "lbm3d_local_slabs": ([H, i32p, i32p, i32, i32p], ctypes.c_int),
+        "lbm3d_exchange_schedule": ([i32, i32, i32, i32, i32, i32, ctypes.POINTER(Xfer), i32, i32p], ctypes.c_int),
+        "lbm3d_run_stats": ([H, i32p, i32p, i32p, i32p], ctypes.c_int),
+        "lbm3d_numerics": ([H], i32),
+        "lbm3d_last_error": ([H], ctypes.c_char_p),
+        "lbm3d_destroy": ([H], None),
+        # include/lbm3d_fields_hip.h
         "lbm3d_store_fields": ([H, f32p, f32p, f32p, f32p, f32p], ctypes.c_int),
         "lbm3d_store_fields_box": ([H, ctypes.POINTER(Box3D), f32p, f32p, f32p, f32p, f32p], ctypes.c_int),
-        "lbm3d_field_stats": ([H, ctypes.POINTER(ctypes.c_double), f32p], ctypes.c_int),
+        "lbm3d_field_stats": ([H, f64p, f32p], ctypes.c_int),
+        # include/lbm_forces_hip.h
         "lbm_wall_force": ([H, f64p, f64p, i64p], ctypes.c_int),
         "lbm_store_wall_force": ([H, f32p, f32p], ctypes.c_int),
         "lbm_set_bodies": ([H, i32p, i32], ctypes.c_int),
@@ -272,37 +284,39 @@ def load_library() -> ctypes.CDLL:
         "lbm3d_store_wall_force": ([H, f32p, f32p, f32p], ctypes.c_int),
         "lbm3d_set_bodies": ([H, i32p, i32], ctypes.c_int),
         "lbm3d_body_forces": ([H, f64p, f64p, f64p, i64p, i32], ctypes.c_int),
-        "lbm3d_last_run_seconds": ([H, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
-        "lbm3d_run_stats": ([H, i32p, i32p, i32p, i32p], ctypes.c_int),
-        "lbm3d_numerics": ([H], i32),
+        # include/lbm_averages_hip.h
         "lbm_avg_begin": ([H, i32], ctypes.c_int),
         "lbm_avg_sample": ([H], ctypes.c_int),
         "lbm_avg_samples": ([H, i64p], ctypes.c_int),
-        "lbm_avg_store_sums": ([H, ctypes.POINTER(f64p)], ctypes.c_int),
-        "lbm_avg_store": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
+        "lbm_avg_store_sums": ([H, f64pp], ctypes.c_int),
+        "lbm_avg_store": ([H, f32pp], ctypes.c_int),
         "lbm_avg_end": ([H], ctypes.c_int),
         "lbm3d_avg_begin": ([H, i32], ctypes.c_int),
         "lbm3d_avg_sample": ([H], ctypes.c_int),
         "lbm3d_avg_samples": ([H, i64p], ctypes.c_int),
-        "lbm3d_avg_store_sums": ([H, ctypes.POINTER(f64p)], ctypes.c_int),
-        "lbm3d_avg_store": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
+        "lbm3d_avg_store_sums": ([H, f64pp], ctypes.c_int),
+        "lbm3d_avg_store": ([H, f32pp], ctypes.c_int),
         "lbm3d_avg_end": ([H], ctypes.c_int),
-        "lbm_store_gradients": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
-        "lbm_store_gradients_local": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
+        # include/lbm_gradients_hip.h
+        "lbm_store_gradients": ([H, f32pp], ctypes.c_int),
+        "lbm_store_gradients_local": ([H, f32pp], ctypes.c_int),
         "lbm_gradient_stats": ([H, f64p, f64p, f32p, f32p], ctypes.c_int),
-        "lbm3d_store_gradients": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
-        "lbm3d_store_gradients_box": ([H, ctypes.POINTER(Box3D), ctypes.POINTER(f32p)], ctypes.c_int),
+        "lbm3d_store_gradients": ([H, f32pp], ctypes.c_int),
+        "lbm3d_store_gradients_box": ([H, ctypes.POINTER(Box3D), f32pp], ctypes.c_int),
         "lbm3d_gradient_stats": ([H, f64p, f64p, f32p, f32p], ctypes.c_int),
-        "lbm_store_stress": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
-        "lbm_store_stress_local": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
+        # include/lbm_stress_hip.h
+        "lbm_store_stress": ([H, f32pp], ctypes.c_int),
+        "lbm_store_stress_local": ([H, f32pp], ctypes.c_int),
         "lbm_stress_stats": ([H, f64p, f32p, i64p, f64p, f32p], ctypes.c_int),
-        "lbm3d_store_stress": ([H, ctypes.POINTER(f32p)], ctypes.c_int),
-        "lbm3d_store_stress_box": ([H, ctypes.POINTER(Box3D), ctypes.POINTER(f32p)], ctypes.c_int),
+        "lbm3d_store_stress": ([H, f32pp], ctypes.c_int),
+        "lbm3d_store_stress_box": ([H, ctypes.POINTER(Box3D), f32pp], ctypes.c_int),
         "lbm3d_stress_stats": ([H, f64p, f32p, i64p, f64p, f32p], ctypes.c_int),
-        "lbm_store_binned": ([H, i32, i32, ctypes.POINTER(f64p)], ctypes.c_int),
+        # include/lbm_binned_hip.h
+        "lbm_store_binned": ([H, i32, i32, f64pp], ctypes.c_int),
         "lbm_bin_fluid_cells": ([H, i32, i32, i64p], ctypes.c_int),
-        "lbm3d_store_binned": ([H, i32, i32, i32, ctypes.POINTER(f64p)], ctypes.c_int),
+        "lbm3d_store_binned": ([H, i32, i32, i32, f64pp], ctypes.c_int),
         "lbm3d_bin_fluid_cells": ([H, i32, i32, i32, i64p], ctypes.c_int),
+        # include/lbm_tracers_hip.h
         "lbm_tracer_begin": ([H, i64, f64p, f64p], ctypes.c_int),
         "lbm_tracer_count": ([H, i64p], ctypes.c_int),
         "lbm_tracer_advance": ([H, ctypes.c_double, i32], ctypes.c_int),
@@ -321,10 +335,6 @@ def load_library() -> ctypes.CDLL:
                                      ctypes.c_int),
         "lbm3d_tracer_sample_ref": ([i32, i32, i32, f32p, f32p, f32p, f32p, i64, f64p, f64p, f64p,
                                      f64p, f64p, f64p, f64p], ctypes.c_int),
-        "lbm3d_total_free_cells": ([H], i64),
-        "lbm3d_local_slabs": ([H, i32p, i32p, i32, i32p], ctypes.c_int),
-        "lbm3d_last_error": ([H], ctypes.c_char_p),
-        "lbm3d_destroy": ([H], None),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -336,12 +346,40 @@ def load_library() -> ctypes.CDLL:
     return L
 
 
-def _f32(a: np.ndarray):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+def _ptr(a: np.ndarray):
+    """The array's data as a pointer to its own element type (float32 -> float *, int64 -> int64_t *, ...)."""
+    return a.ctypes.data_as(ctypes.POINTER(np.ctypeslib.as_ctypes_type(a.dtype)))
 
 
-def _f64(a: np.ndarray):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+def _select(names, which, what):
+    """`which` (None: all of `names`) as a tuple, checked; `what` names the kind of field in the error."""
+    which = tuple(names if which is None else which)
+    if any(n not in names for n in which) or len(set(which)) != len(which):
+        raise ValueError(f"{what} are a subset of {names}, each at most once; got {which}")
+    return which
+
+
+def _ptr_list(names, out):
+    """One pointer per header name, None (NULL) where `out` has no such array: the positional form."""
+    return [_ptr(out[n]) if n in out else None for n in names]
+
+
+def _ptr_table(names, out, ctype):
+    """The same as the `ctype *out[len(names)]` array the store entry points take."""
+    return (ctypes.POINTER(ctype) * len(names))(*_ptr_list(names, out))
+
+
+def _per_rect(rects, packed, *tail):
+    """Views [h][w][*tail] per rect (local_rects() order) of a packed array, or of each of a dict of them."""
+    out, off = [], 0
+    for (_, _, w, h) in rects:
+        n = w * h * int(np.prod(tail, dtype=np.int64))
+        if isinstance(packed, dict):
+            out.append({f: a[off:off + n].reshape(h, w, *tail) for f, a in packed.items()})
+        else:
+            out.append(packed[off:off + n].reshape(h, w, *tail))
+        off += n
+    return out
 
 
 def _tracer_scheme(scheme) -> int:
@@ -374,7 +412,7 @@ def tracer_advance_ref(ux, uy, x, y, dt, scheme="heun"):
     L = load_library()
     (ux, uy), (nx, ny) = _ref_fields((ux, uy), 2)
     x, y = _ref_points((x, y))
-    rc = L.lbm_tracer_advance_ref(nx, ny, _f32(ux), _f32(uy), x.size, _f64(x), _f64(y), float(dt),
+    rc = L.lbm_tracer_advance_ref(nx, ny, _ptr(ux), _ptr(uy), x.size, _ptr(x), _ptr(y), float(dt),
                                   _tracer_scheme(scheme))
     if rc != LBM_OK:
         raise LbmError(rc, "lbm_tracer_advance_ref: invalid argument")
@@ -386,7 +424,7 @@ def tracer_advance3d_ref(ux, uy, uz, x, y, z, dt, scheme="heun"):
     L = load_library()
     (ux, uy, uz), (nx, ny, nz) = _ref_fields((ux, uy, uz), 3)
     x, y, z = _ref_points((x, y, z))
-    rc = L.lbm3d_tracer_advance_ref(nx, ny, nz, _f32(ux), _f32(uy), _f32(uz), x.size, _f64(x), _f64(y), _f64(z),
+    rc = L.lbm3d_tracer_advance_ref(nx, ny, nz, _ptr(ux), _ptr(uy), _ptr(uz), x.size, _ptr(x), _ptr(y), _ptr(z),
                                     float(dt), _tracer_scheme(scheme))
     if rc != LBM_OK:
         raise LbmError(rc, "lbm3d_tracer_advance_ref: invalid argument")
@@ -399,8 +437,8 @@ def _sample_ref(fn, names, fields, pos):
     pts = _ref_points(pos)
     nan = np.float64(np.nan)
     out = {n: np.full(pts[0].size, nan) for n, a in zip(names, arrs) if a is not None}
-    rc = fn(*extent, *[None if a is None else _f32(a) for a in arrs], pts[0].size, *[_f64(c) for c in pts],
-            *[_f64(out[n]) if n in out else None for n in names])
+    rc = fn(*extent, *[None if a is None else _ptr(a) for a in arrs], pts[0].size, *[_ptr(c) for c in pts],
+            *_ptr_list(names, out))
     if rc != LBM_OK:
         raise LbmError(rc, "tracer_sample_ref: invalid argument")
     return out
@@ -479,152 +517,192 @@ def rccl_unique_id() -> bytes:
     return bytes(buf)
 
 
+class _Handle:
+    """What Engine and Engine3D share: the handle's life, the lookup of the engine's C functions,
+    the error check and the chunked-run driver.  The class sets _PREFIX ("lbm_" / "lbm3d_") and
+    _shape() (the domain's extents, slowest axis first); the diagnostics' mixins below use both."""
+
+    def _fn(self, name):
+        return getattr(self._L, self._PREFIX + name)
+
+    def _check(self, rc: int):
+        if rc != LBM_OK:
+            raise LbmError(rc, self._fn("last_error")(self._h).decode())
+
+    def _config(self, devices, unique_id) -> Config:
+        """A Config with the device list and the RCCL id set; both buffers live as long as the handle."""
+        cfg = Config()
+        if devices:
+            self._devs = (ctypes.c_int32 * len(devices))(*devices)
+            cfg.devices = self._devs
+            cfg.num_devices = len(devices)
+        if unique_id is not None:
+            self._uid = (ctypes.c_uint8 * 128).from_buffer_copy(unique_id)
+            cfg.rccl_unique_id = self._uid
+        return cfg
+
+    def _create(self, name, obst, cfg) -> None:
+        self._h = ctypes.c_void_p()
+        rc = self._fn(name)(ctypes.byref(self.params), _ptr(obst), ctypes.byref(cfg), ctypes.byref(self._h))
+        if rc != LBM_OK:
+            raise LbmError(rc, self._fn("last_error")(None).decode())
+
+    def _store_fields(self, name, names, which, shape, dtype, *args, table=True):
+        """{n: zeros(shape) for n in which}, filled by the engine's `name`(handle, *args, outputs): the
+        outputs as one pointer table, or (table=False) as one positional pointer per header name."""
+        out = {n: np.zeros(shape, dtype) for n in which}
+        ptrs = [_ptr_table(names, out, np.ctypeslib.as_ctypes_type(dtype))] if table else _ptr_list(names, out)
+        self._check(self._fn(name)(self._h, *args, *ptrs))
+        return out
+
+    def _chunks(self, steps, every, accelerate_first, collect_av, after):
+        """Advance `steps` steps in run_steps(every) chunks (the remainder last; accelerate_first on the
+        first chunk, D2Q9 only) and call after(n, done) behind each.  Returns the float32 concatenation
+        of the chunks' average velocities where collect_av asks for them (D2Q9 only), else an empty one."""
+        steps, every = int(steps), int(every)
+        if steps < 0 or every < 1:
+            raise ValueError("steps >= 0 and every >= 1")
+        two_d = len(self._shape()) == 2
+        if accelerate_first and not two_d:
+            raise ValueError("accelerate_first applies to the D2Q9 engine only")
+        av, done = [], 0
+        while done < steps:
+            n = min(every, steps - done)
+            if two_d:
+                self.run_steps(n, accelerate_first and done == 0)
+                if collect_av:
+                    av.append(self.store(cells=False, n_av=n)[1].copy())
+            else:
+                self.run_steps(n)
+            done += n
+            after(n, done)
+        return np.concatenate(av) if av else np.zeros(0, np.float32)
+
+    def _stat_history(self, steps, every, accelerate_first, stats):
+        """([(step,) + stats() after each chunk], av_vels) of _chunks."""
+        samples = []
+        av = self._chunks(steps, every, accelerate_first, True, lambda n, done: samples.append((done,) + stats()))
+        return samples, av
+
+    def close(self) -> None:
+        if self._h:
+            self._fn("destroy")(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class _WallForces:
-    """Engine / Engine3D methods over include/lbm_forces_hip.h; the class sets
-    _FORCE_PREFIX ("lbm_" / "lbm3d_") and _force_shape()."""
+    """Engine / Engine3D methods over include/lbm_forces_hip.h."""
 
     _nbodies = 0
-
-    def _force_fn(self, name):
-        return getattr(self._L, self._FORCE_PREFIX + name)
 
     def wall_force(self):
         """(fx, fy[, fz], links): the momentum-exchange force the fluid put on all wall
         cells of this handle's sub-domains in the last step (fp64 sums of the fp32
         per-cell values, folded in a fixed order) and the number of links."""
-        dims = len(self._force_shape())
-        f = [ctypes.c_double() for _ in range(dims)]
+        f = [ctypes.c_double() for _ in self._shape()]
         links = ctypes.c_int64()
-        self._check(self._force_fn("wall_force")(self._h, *[ctypes.byref(v) for v in f], ctypes.byref(links)))
+        self._check(self._fn("wall_force")(self._h, *[ctypes.byref(v) for v in f], ctypes.byref(links)))
         return tuple(v.value for v in f) + (links.value,)
 
     def wall_force_field(self):
         """(fx, fy[, fz]): planar float32 maps of the per-cell force, +0 on every cell that
         is no wall cell -- lio.wall_force_cells of store()'s cells, bit for bit.  RCCL:
         only this rank's part is written."""
-        out = [np.zeros(self._force_shape(), np.float32) for _ in self._force_shape()]
-        self._check(self._force_fn("store_wall_force")(self._h, *[_f32(a) for a in out]))
+        out = [np.zeros(self._shape(), np.float32) for _ in self._shape()]
+        self._check(self._fn("store_wall_force")(self._h, *[_ptr(a) for a in out]))
         return tuple(out)
 
     def set_bodies(self, labels, nbodies: int) -> None:
         """Assign blocked cells to bodies 0..nbodies-1 (labels: int32 map of the full
         domain, e.g. lio.label_bodies; negative = no body).  set_bodies(None, 0) clears."""
         if labels is None:
-            self._check(self._force_fn("set_bodies")(self._h, None, int(nbodies)))
+            self._check(self._fn("set_bodies")(self._h, None, int(nbodies)))
         else:
             lab = np.ascontiguousarray(labels, dtype=np.int32)
-            if lab.size != int(np.prod(self._force_shape())):
+            if lab.size != int(np.prod(self._shape())):
                 raise ValueError("labels must cover the full domain")
-            self._check(self._force_fn("set_bodies")(self._h, lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                                     int(nbodies)))
+            self._check(self._fn("set_bodies")(self._h, _ptr(lab), int(nbodies)))
         self._nbodies = int(nbodies) if labels is not None else 0
 
     def body_forces(self):
         """(fx[nbodies], fy[nbodies][, fz[nbodies]], links[nbodies]) of the bodies set last,
         summed on the device."""
         n = self._nbodies
-        dims = len(self._force_shape())
-        f = [np.zeros(max(n, 1), np.float64) for _ in range(dims)]
+        f = [np.zeros(max(n, 1), np.float64) for _ in self._shape()]
         links = np.zeros(max(n, 1), np.int64)
-        self._check(self._force_fn("body_forces")(
-            self._h, *[a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) for a in f],
-            links.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n))
+        self._check(self._fn("body_forces")(self._h, *[_ptr(a) for a in f], _ptr(links), n))
         return tuple(a[:n] for a in f) + (links[:n],)
 
 
 class _Averages:
-    """Engine / Engine3D methods over include/lbm_averages_hip.h; the class sets
-    _FORCE_PREFIX ("lbm_" / "lbm3d_"), _force_shape() and _AVG_FIELDS."""
+    """Engine / Engine3D methods over include/lbm_averages_hip.h; the class sets _AVG_FIELDS."""
 
-    def _avg_fn(self, name):
-        return getattr(self._L, self._FORCE_PREFIX + "avg_" + name)
-
-    def _avg_which(self, which):
+    def _avg_store(self, name, which, dtype):
+        """`which` defaults to every field begun: the first moments only after avg_begin(second=False)."""
         names = self._AVG_FIELDS
-        which = names if which is None else tuple(which)
-        bad = [n for n in which if n not in names]
-        if bad or len(set(which)) != len(which):
-            raise ValueError(f"averaged fields are a subset of {names}, each at most once; got {which}")
-        return which
-
-    def _avg_store(self, fn, which, dtype, ctype):
-        out = {n: np.zeros(self._force_shape(), dtype) for n in which}
-        ptrs = (ctypes.POINTER(ctype) * len(self._AVG_FIELDS))()
-        for i, n in enumerate(self._AVG_FIELDS):
-            if n in out:
-                ptrs[i] = out[n].ctypes.data_as(ctypes.POINTER(ctype))
-        self._check(fn(self._h, ptrs))
-        return out
+        if which is None and not getattr(self, "_avg_second", True):
+            which = names[:len(self._shape()) + 1]
+        which = _select(names, which, "averaged fields")
+        return self._store_fields(name, names, which, self._shape(), dtype)
 
     def avg_begin(self, second: bool = True) -> None:
         """Start (or restart, re-zeroed) averaging: one fp64 sum per cell beside the lattice
         for the first moments (ux, uy[, uz], pressure) and, with `second`, for the velocity
         products and pressure squared.  8 B x fields x cells of device memory."""
-        self._check(self._avg_fn("begin")(self._h, AVG_MEAN | AVG_SECOND if second else AVG_MEAN))
+        self._check(self._fn("avg_begin")(self._h, AVG_MEAN | AVG_SECOND if second else AVG_MEAN))
         self._avg_second = bool(second)
 
     def avg_sample(self) -> None:
         """Add the current lattice to the sums (one kernel; nothing goes to the host)."""
-        self._check(self._avg_fn("sample")(self._h))
+        self._check(self._fn("avg_sample")(self._h))
 
     @property
     def avg_samples(self) -> int:
         n = ctypes.c_int64()
-        self._check(self._avg_fn("samples")(self._h, ctypes.byref(n)))
+        self._check(self._fn("avg_samples")(self._h, ctypes.byref(n)))
         return n.value
 
     def avg_end(self) -> None:
         """Free the accumulators (close() frees them too)."""
-        self._check(self._avg_fn("end")(self._h))
-
-    def _avg_default(self):
-        names = self._AVG_FIELDS
-        return names if getattr(self, "_avg_second", True) else names[:len(self._force_shape()) + 1]
+        self._check(self._fn("avg_end")(self._h))
 
     def avg_sums(self, which=None):
         """{name: float64 array} of the raw sums (lbm_avg_store_sums): lio.moment_sums of the
         sampled fields(), bit for bit.  Default: every field begun.  RCCL: only this rank's
         part is written."""
-        which = self._avg_which(self._avg_default() if which is None else which)
-        return self._avg_store(self._avg_fn("store_sums"), which, np.float64, ctypes.c_double)
+        return self._avg_store("avg_store_sums", which, np.float64)
 
     def mean_fields(self, which=None):
         """{name: float32 array}: the time means of "ux", "uy"[, "uz"], "pressure" and, under
         the second-moment names ("uxux", "uxuy", ..., "pp"), the central moments
         <a b> - <a><b> (Reynolds stresses, pressure variance), formed on the device
         (lbm_avg_store): lio.moment_means of avg_sums(), bit for bit."""
-        which = self._avg_which(self._avg_default() if which is None else which)
-        return self._avg_store(self._avg_fn("store"), which, np.float32, ctypes.c_float)
+        return self._avg_store("avg_store", which, np.float32)
 
 
 class _Gradients:
-    """Engine / Engine3D methods over include/lbm_gradients_hip.h; the class sets
-    _FORCE_PREFIX ("lbm_" / "lbm3d_"), _force_shape() and _GRAD_FIELDS."""
-
-    def _grad_which(self, which):
-        names = self._GRAD_FIELDS
-        which = names if which is None else tuple(which)
-        bad = [n for n in which if n not in names]
-        if bad or len(set(which)) != len(which):
-            raise ValueError(f"gradient fields are a subset of {names}, each at most once; got {which}")
-        return which
-
-    def _grad_ptrs(self, out):
-        ptrs = (ctypes.POINTER(ctypes.c_float) * len(self._GRAD_FIELDS))()
-        for i, n in enumerate(self._GRAD_FIELDS):
-            if n in out:
-                ptrs[i] = _f32(out[n])
-        return ptrs
+    """Engine / Engine3D methods over include/lbm_gradients_hip.h; the class sets _GRAD_FIELDS."""
 
     def gradients(self, which=None):
         """{name: float32 array} of the requested fields ("vorticity", "divergence",
         "strain", "q"; D3Q19 also "wx", "wy", "wz"), derived on the device from the
         current lattice (lbm_store_gradients): lio.velocity_gradients[3d] of fields(), bit
         for bit.  Default: every field."""
-        which = self._grad_which(which)
-        out = {n: np.zeros(self._force_shape(), np.float32) for n in which}
-        self._check(getattr(self._L, self._FORCE_PREFIX + "store_gradients")(self._h, self._grad_ptrs(out)))
-        return out
+        names = self._GRAD_FIELDS
+        return self._store_fields("store_gradients", names, _select(names, which, "gradient fields"), self._shape(),
+                                  np.float32)
 
     def gradient_stats(self):
         """(sum_w2, sum_s2, max_w, max_div) over this handle's fluid cells
@@ -632,39 +710,22 @@ class _Gradients:
         |vorticity| and |divergence|.  Enstrophy = sum_w2 / 2; dissipation = 2 nu sum_s2."""
         w2, s2 = ctypes.c_double(), ctypes.c_double()
         mw, md = ctypes.c_float(), ctypes.c_float()
-        self._check(getattr(self._L, self._FORCE_PREFIX + "gradient_stats")(
+        self._check(self._fn("gradient_stats")(
             self._h, ctypes.byref(w2), ctypes.byref(s2), ctypes.byref(mw), ctypes.byref(md)))
         return w2.value, s2.value, mw.value, md.value
 
 
 class _Stress:
-    """Engine / Engine3D methods over include/lbm_stress_hip.h; the class sets
-    _FORCE_PREFIX ("lbm_" / "lbm3d_"), _force_shape() and _STRESS_FIELDS."""
-
-    def _stress_which(self, which):
-        names = self._STRESS_FIELDS
-        which = names if which is None else tuple(which)
-        bad = [n for n in which if n not in names]
-        if bad or len(set(which)) != len(which):
-            raise ValueError(f"strain-rate fields are a subset of {names}, each at most once; got {which}")
-        return which
-
-    def _stress_ptrs(self, out):
-        ptrs = (ctypes.POINTER(ctypes.c_float) * len(self._STRESS_FIELDS))()
-        for i, n in enumerate(self._STRESS_FIELDS):
-            if n in out:
-                ptrs[i] = _f32(out[n])
-        return ptrs
+    """Engine / Engine3D methods over include/lbm_stress_hip.h; the class sets _STRESS_FIELDS."""
 
     def strain_rate(self, which=None):
         """{name: float32 array} of the requested strain-rate components and "strain"
         (D2Q9: "sxx", "sxy", "syy"; D3Q19 also "szz", "sxz", "syz"), from the
         non-equilibrium moments of the current lattice on the device (lbm_store_stress):
         lio.neq_strain[3d] of store()'s cells, bit for bit.  Default: every field."""
-        which = self._stress_which(which)
-        out = {n: np.zeros(self._force_shape(), np.float32) for n in which}
-        self._check(getattr(self._L, self._FORCE_PREFIX + "store_stress")(self._h, self._stress_ptrs(out)))
-        return out
+        names = self._STRESS_FIELDS
+        return self._store_fields("store_stress", names, _select(names, which, "strain-rate fields"), self._shape(),
+                                  np.float32)
 
     def strain_stats(self):
         """(sum_s2, max_strain, wall_cells, sum_wall_strain, max_wall_strain) over this
@@ -674,25 +735,16 @@ class _Stress:
         s2, sw = ctypes.c_double(), ctypes.c_double()
         ms, mw = ctypes.c_float(), ctypes.c_float()
         nw = ctypes.c_int64()
-        self._check(getattr(self._L, self._FORCE_PREFIX + "stress_stats")(
+        self._check(self._fn("stress_stats")(
             self._h, ctypes.byref(s2), ctypes.byref(ms), ctypes.byref(nw), ctypes.byref(sw), ctypes.byref(mw)))
         return s2.value, ms.value, nw.value, sw.value, mw.value
 
 
 class _Binned:
-    """Engine / Engine3D methods over include/lbm_binned_hip.h; the class sets
-    _FORCE_PREFIX ("lbm_" / "lbm3d_"), _force_shape() and _BIN_FIELDS."""
-
-    def _bin_which(self, which):
-        names = self._BIN_FIELDS
-        which = names if which is None else tuple(which)
-        bad = [n for n in which if n not in names]
-        if bad or len(set(which)) != len(which):
-            raise ValueError(f"binned fields are a subset of {names}, each at most once; got {which}")
-        return which
+    """Engine / Engine3D methods over include/lbm_binned_hip.h; the class sets _BIN_FIELDS."""
 
     def _bin_shape(self, bins):
-        shape = self._force_shape()                      # slowest axis first
+        shape = self._shape()                            # slowest axis first
         if len(bins) != len(shape):
             raise ValueError(f"{len(shape)} bin sizes (x, y[, z]) expected; got {bins}")
         return tuple(-(-n // max(int(b), 1)) for n, b in zip(shape, bins[::-1]))
@@ -705,8 +757,7 @@ class _Binned:
         cache = self.__dict__.setdefault("_bin_fluid", {})
         if bins not in cache:
             count = np.zeros(self._bin_shape(bins), np.int64)
-            self._check(getattr(self._L, self._FORCE_PREFIX + "bin_fluid_cells")(
-                self._h, *bins, count.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+            self._check(self._fn("bin_fluid_cells")(self._h, *bins, _ptr(count)))
             cache[bins] = count
         return cache[bins].copy()
 
@@ -718,13 +769,9 @@ class _Binned:
         them; lio.binned_means divides.  Default: every field.  RCCL: this rank's partial
         sums and counts over the full bin grid."""
         bins = tuple(int(b) for b in bins)
-        which = self._bin_which(which)
-        out = {n: np.zeros(self._bin_shape(bins), np.float64) for n in which}
-        ptrs = (ctypes.POINTER(ctypes.c_double) * len(self._BIN_FIELDS))()
-        for i, n in enumerate(self._BIN_FIELDS):
-            if n in out:
-                ptrs[i] = out[n].ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-        self._check(getattr(self._L, self._FORCE_PREFIX + "store_binned")(self._h, *bins, ptrs))
+        names = self._BIN_FIELDS
+        out = self._store_fields("store_binned", names, _select(names, which, "binned fields"), self._bin_shape(bins),
+                                 np.float64, *bins)
         out["fluid"] = self.bin_fluid_cells(*bins)
         return out
 
@@ -736,40 +783,37 @@ class _Binned:
     def profile_y(self, which=None):
         """{name: float64[ny]}: the means over x (D3Q19: over x and z) of the requested
         quantities per row y -- the profile across the channel.  Bins (nx, 1[, nz])."""
-        shape = self._force_shape()
+        shape = self._shape()
         bins = (shape[-1], 1) + ((shape[0],) if len(shape) == 3 else ())
         return {n: a.reshape(-1) for n, a in self._bin_means(bins, which).items()}
 
     def flux_x(self):
         """float64[nx]: the sum of rho u_x over every cross-section x = const (the "jx"
         sums of bins (1, ny[, nz])): the mass flux through it."""
-        shape = self._force_shape()
+        shape = self._shape()
         return self.binned(*((1,) + shape[::-1][1:]), which=("jx",))["jx"].reshape(-1)
 
     def coarse_fields(self, k: int):
         """{name: float64 array} of the k x k[ x k] block means of "ux", "uy"[, "uz"] and
         "speed" over the fluid cells of each block (0 where a block holds none)."""
-        dims = len(self._force_shape())
+        dims = len(self._shape())
         which = ("ux", "uy", "uz", "speed") if dims == 3 else ("ux", "uy", "speed")
-        bins = tuple(min(int(k), n) for n in self._force_shape()[::-1])
+        bins = tuple(min(int(k), n) for n in self._shape()[::-1])
         return self._bin_means(bins, which)
 
     def binned_history(self, steps: int, every: int, *bins, which=None):
         """Advance `steps` steps in run_steps(every) chunks (the remainder last) and take
         binned(*bins, which) after each chunk.  Returns {name: float64[samples, ...]} of
         the stacked samples, "step": the steps done at each sample, and "fluid".  The
-        operator is linear: sums of the samples over time are the binned time sums."""
-        steps, every = int(steps), int(every)
-        if steps < 0 or every < 1:
-            raise ValueError("steps >= 0 and every >= 1")
-        which = self._bin_which(which)
-        samples, at, done = [], [], 0
-        while done < steps:
-            n = min(every, steps - done)
-            self.run_steps(n)
-            done += n
+        operator is linear: sums of the samples over time are the binned time sums.
+        No average velocities are collected."""
+        which = _select(self._BIN_FIELDS, which, "binned fields")
+        samples, at = [], []
+
+        def after(n, done):
             samples.append(self.binned(*bins, which=which))
             at.append(done)
+        self._chunks(steps, every, False, False, after)
         shape = self._bin_shape(tuple(int(b) for b in bins))
         out = {n: (np.stack([s[n] for s in samples]) if samples else np.zeros((0,) + shape)) for n in which}
         out["step"] = np.asarray(at, np.int64)
@@ -778,86 +822,53 @@ class _Binned:
 
 
 class _Tracers:
-    """Engine / Engine3D methods over include/lbm_tracers_hip.h; the class sets
-    _FORCE_PREFIX ("lbm_" / "lbm3d_"), _force_shape() and _TRACER_FIELDS."""
-
-    def _tracer_fn(self, name):
-        return getattr(self._L, self._FORCE_PREFIX + "tracer_" + name)
-
-    def _tracer_which(self, which):
-        names = self._TRACER_FIELDS
-        which = names if which is None else tuple(which)
-        bad = [n for n in which if n not in names]
-        if bad or len(set(which)) != len(which):
-            raise ValueError(f"sampled fields are a subset of {names}, each at most once; got {which}")
-        return which
+    """Engine / Engine3D methods over include/lbm_tracers_hip.h; the class sets _TRACER_FIELDS."""
 
     def tracers_begin(self, x, y, z=None) -> None:
         """Copy the seed points (cell units, 0 <= x < nx, ...; float64) to the device; a second
         call replaces the set.  16 B (24 B) of device memory per point."""
-        dims = len(self._force_shape())
+        dims = len(self._shape())
         pos = (x, y) if dims == 2 else (x, y, z)
         if (z is None) != (dims == 2):
             raise ValueError(f"{dims} coordinate arrays expected")
         pts = [np.ascontiguousarray(c, np.float64).reshape(-1) for c in pos]
         if len({c.size for c in pts}) != 1:
             raise ValueError("coordinate arrays must have one length")
-        self._check(self._tracer_fn("begin")(self._h, pts[0].size, *[_f64(c) for c in pts]))
+        self._check(self._fn("tracer_begin")(self._h, pts[0].size, *[_ptr(c) for c in pts]))
 
     @property
     def tracer_count(self) -> int:
         n = ctypes.c_int64()
-        self._check(self._tracer_fn("count")(self._h, ctypes.byref(n)))
+        self._check(self._fn("tracer_count")(self._h, ctypes.byref(n)))
         return n.value
 
     def tracers_advance(self, dt, scheme="heun") -> None:
         """Move every point by dt lattice steps of the current lattice's velocity (one gather
         kernel; nothing goes to the host): lio.tracer_advance[3d] of fields(), bit for bit."""
-        self._check(self._tracer_fn("advance")(self._h, float(dt), _tracer_scheme(scheme)))
+        self._check(self._fn("tracer_advance")(self._h, float(dt), _tracer_scheme(scheme)))
 
     def tracers(self):
         """{"x", "y"[, "z"]: float64[n], "blocked": uint8[n]}: the current positions and whether
         the nearest cell of each is an obstacle."""
         n = self.tracer_count
-        names = ("x", "y", "z")[:len(self._force_shape())]
+        names = ("x", "y", "z")[:len(self._shape())]
         out = {c: np.full(n, np.nan) for c in names}
         out["blocked"] = np.zeros(n, np.uint8)
-        self._check(self._tracer_fn("store")(self._h, *[_f64(out[c]) for c in names],
-                                             out["blocked"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+        self._check(self._fn("tracer_store")(self._h, *[_ptr(out[c]) for c in names], _ptr(out["blocked"])))
         return out
 
     def tracer_sample(self, which=None):
         """{name: float64[n]} of "ux", "uy"[, "uz"], "pressure" interpolated at the current
         positions: lio.tracer_interp[3d] of fields(), bit for bit.  Default: every field."""
-        which = self._tracer_which(which)
+        which = _select(self._TRACER_FIELDS, which, "sampled fields")
         n = self.tracer_count
         out = {f: np.full(n, np.nan) for f in which}
-        self._check(self._tracer_fn("sample")(self._h, *[_f64(out[f]) if f in out else None
-                                                         for f in self._TRACER_FIELDS]))
+        self._check(self._fn("tracer_sample")(self._h, *_ptr_list(self._TRACER_FIELDS, out)))
         return out
 
     def tracers_end(self) -> None:
         """Free the set (close() frees it too)."""
-        self._check(self._tracer_fn("end")(self._h))
-
-    def _traced_chunks(self, steps, every, accelerate_first, after):
-        steps, every = int(steps), int(every)
-        if steps < 0 or every < 1:
-            raise ValueError("steps >= 0 and every >= 1")
-        two_d = len(self._force_shape()) == 2
-        if accelerate_first and not two_d:
-            raise ValueError("accelerate_first applies to the D2Q9 engine only")
-        av, done = [], 0
-        while done < steps:
-            n = min(every, steps - done)
-            if two_d:
-                self.run_steps(n, accelerate_first and done == 0)
-                av.append(self.store(cells=False, n_av=n)[1].copy())
-            else:
-                self.run_steps(n)
-            done += n
-            after(n, done)
-        return np.concatenate(av) if av else np.zeros(0, np.float32)
+        self._check(self._fn("tracer_end")(self._h))
 
     def run_traced(self, steps: int, every: int, scheme="heun", accelerate_first: bool = False):
         """Advance `steps` steps in run_steps(every) chunks (the remainder last) and move the
@@ -865,139 +876,33 @@ class _Tracers:
         shorter last chunk gets its own dt.  Returns the float32[steps] concatenation of the
         chunks' average velocities (D3Q19: empty).  Chunking behaves as in run_averaged."""
         scheme = _tracer_scheme(scheme)
-        return self._traced_chunks(steps, every, accelerate_first, lambda n, done: self.tracers_advance(n, scheme))
+        return self._chunks(steps, every, accelerate_first, True, lambda n, done: self.tracers_advance(n, scheme))
 
     def probe_history(self, steps: int, every: int, which=None, accelerate_first: bool = False):
         """The same chunks without moving the points: tracer_sample(which) after each chunk.
         Returns {name: float64[samples, n]} and "step": the steps done at each sample."""
-        which = self._tracer_which(which)
+        which = _select(self._TRACER_FIELDS, which, "sampled fields")
         samples, at = [], []
 
         def after(n, done):
             samples.append(self.tracer_sample(which))
             at.append(done)
-        self._traced_chunks(steps, every, accelerate_first, after)
+        self._chunks(steps, every, accelerate_first, True, after)
         n = self.tracer_count
         out = {f: (np.stack([s[f] for s in samples]) if samples else np.zeros((0, n))) for f in which}
         out["step"] = np.asarray(at, np.int64)
         return out
 
 
-class Engine(_WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
+class Engine(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
     """One lbm_handle: the HIP counterpart of the reference's poplar::Engine."""
 
-    _FORCE_PREFIX = "lbm_"
+    _PREFIX = "lbm_"
     _AVG_FIELDS = AVG_FIELDS
     _GRAD_FIELDS = GRAD_FIELDS
     _STRESS_FIELDS = STRESS_FIELDS
     _BIN_FIELDS = BIN_FIELDS
     _TRACER_FIELDS = TRACER_FIELDS
-
-    def strain_rate_local(self, which=None):
-        """[{name: float32[h][w]}] per local rect (local_rects() order; lbm_store_stress_local)."""
-        which = self._stress_which(which)
-        rects = self.local_rects()
-        n = int(self._L.lbm_local_cells(self._h))
-        packed = {f: np.zeros(n, np.float32) for f in which}
-        self._check(self._L.lbm_store_stress_local(self._h, self._stress_ptrs(packed)))
-        out, off = [], 0
-        for (_, _, w, h) in rects:
-            out.append({f: packed[f][off:off + w * h].reshape(h, w) for f in which})
-            off += w * h
-        return out
-
-    def strain_history(self, steps: int, every: int, accelerate_first: bool = False):
-        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and sample
-        strain_stats() after each chunk.  Returns (samples, av_vels): samples is a list of
-        (step, sum_s2, max_strain, wall_cells, sum_wall_strain, max_wall_strain), av_vels the
-        float32[steps] concatenation of the chunks' average velocities.  Chunking behaves
-        as in force_history."""
-        steps, every = int(steps), int(every)
-        if steps < 0 or every < 1:
-            raise ValueError("steps >= 0 and every >= 1")
-        samples, av, done = [], [], 0
-        while done < steps:
-            n = min(every, steps - done)
-            self.run_steps(n, accelerate_first and done == 0)
-            av.append(self.store(cells=False, n_av=n)[1].copy())
-            done += n
-            samples.append((done,) + self.strain_stats())
-        return samples, (np.concatenate(av) if av else np.zeros(0, np.float32))
-
-    def gradients_local(self, which=None):
-        """[{name: float32[h][w]}] per local rect (local_rects() order; lbm_store_gradients_local)."""
-        which = self._grad_which(which)
-        rects = self.local_rects()
-        n = int(self._L.lbm_local_cells(self._h))
-        packed = {f: np.zeros(n, np.float32) for f in which}
-        self._check(self._L.lbm_store_gradients_local(self._h, self._grad_ptrs(packed)))
-        out, off = [], 0
-        for (_, _, w, h) in rects:
-            out.append({f: packed[f][off:off + w * h].reshape(h, w) for f in which})
-            off += w * h
-        return out
-
-    def gradient_history(self, steps: int, every: int, accelerate_first: bool = False):
-        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and sample
-        gradient_stats() after each chunk.  Returns (samples, av_vels): samples is a list of
-        (step, sum_w2, sum_s2, max_w, max_div) with step = steps done so far, av_vels the
-        float32[steps] concatenation of the chunks' average velocities.  Chunking behaves
-        as in force_history."""
-        steps, every = int(steps), int(every)
-        if steps < 0 or every < 1:
-            raise ValueError("steps >= 0 and every >= 1")
-        samples, av, done = [], [], 0
-        while done < steps:
-            n = min(every, steps - done)
-            self.run_steps(n, accelerate_first and done == 0)
-            av.append(self.store(cells=False, n_av=n)[1].copy())
-            done += n
-            samples.append((done,) + self.gradient_stats())
-        return samples, (np.concatenate(av) if av else np.zeros(0, np.float32))
-
-    def run_averaged(self, steps: int, every: int, accelerate_first: bool = False):
-        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and
-        avg_sample() after each chunk (avg_begin first).  Returns the float32[steps]
-        concatenation of the chunks' average velocities.  accelerate_first applies to the
-        first chunk only.  In bitwise mode the lattice and av_vels equal those of one
-        run_steps(steps).  In tolerance mode a chunked run differs from an unchunked one
-        in the last bits: the steps of a chunk that do not fill a fused launch run as
-        remainder launches, and remainder launches are bitwise."""
-        steps, every = int(steps), int(every)
-        if steps < 0 or every < 1:
-            raise ValueError("steps >= 0 and every >= 1")
-        av, done = [], 0
-        while done < steps:
-            n = min(every, steps - done)
-            self.run_steps(n, accelerate_first and done == 0)
-            av.append(self.store(cells=False, n_av=n)[1].copy())
-            done += n
-            self.avg_sample()
-        return np.concatenate(av) if av else np.zeros(0, np.float32)
-
-    def _force_shape(self):
-        return (self.params.ny, self.params.nx)
-
-    def force_history(self, steps: int, every: int, accelerate_first: bool = False):
-        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and sample
-        wall_force() after each chunk.  Returns (samples, av_vels): samples is a list of
-        (step, fx, fy, links) with step = steps done so far, av_vels the float32[steps]
-        concatenation of the chunks' average velocities.  accelerate_first applies to the
-        first chunk only.  In bitwise mode the lattice and av_vels equal those of one
-        run_steps(steps).  In tolerance mode a chunked run differs from an unchunked one
-        in the last bits: the steps of a chunk that do not fill a fused launch run as
-        remainder launches, and remainder launches are bitwise."""
-        steps, every = int(steps), int(every)
-        if steps < 0 or every < 1:
-            raise ValueError("steps >= 0 and every >= 1")
-        samples, av, done = [], [], 0
-        while done < steps:
-            n = min(every, steps - done)
-            self.run_steps(n, accelerate_first and done == 0)
-            av.append(self.store(cells=False, n_av=n)[1].copy())
-            done += n
-            samples.append((done,) + self.wall_force())
-        return samples, (np.concatenate(av) if av else np.zeros(0, np.float32))
 
     def __init__(self, params, obstacles: np.ndarray, num_gpus: int = 1, *, parts: int | None = None,
                  grid=(0, 0), transport: int = TRANSPORT_LOCAL, rank: int = 0, world: int = 1,
@@ -1009,37 +914,77 @@ class Engine(_WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
         obst = np.ascontiguousarray(obstacles, dtype=np.uint8)
         if obst.size != self.params.nx * self.params.ny:
             raise ValueError("obstacles must have ny*nx entries")
-        self._h = ctypes.c_void_p()
-        cfg = Config()
+        cfg = self._config(devices, unique_id)
         cfg.parts = int(parts if parts is not None else (world if transport == TRANSPORT_RCCL else num_gpus))
         cfg.grid_rows, cfg.grid_cols = int(grid[0]), int(grid[1])
         cfg.transport = transport
         cfg.rank, cfg.world = int(rank), int(world)
-        if devices:
-            self._devs = (ctypes.c_int32 * len(devices))(*devices)
-            cfg.devices = self._devs
-            cfg.num_devices = len(devices)
-        if unique_id is not None:
-            self._uid = (ctypes.c_uint8 * 128).from_buffer_copy(unique_id)
-            cfg.rccl_unique_id = self._uid
         cfg.kernel = kernel
         cfg.graph_steps = graph_steps
         cfg.flags = flags
         cfg.steps_per_launch = int(steps_per_launch)
-        rc = self._L.lbm_create_ex(ctypes.byref(self.params), obst.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                   ctypes.byref(cfg), ctypes.byref(self._h))
-        if rc != LBM_OK:
-            raise LbmError(rc, self._L.lbm_last_error(None).decode())
+        self._create("create_ex", obst, cfg)
 
-    def _check(self, rc: int):
-        if rc != LBM_OK:
-            raise LbmError(rc, self._L.lbm_last_error(self._h).decode())
+    def _shape(self):
+        return (self.params.ny, self.params.nx)
+
+    def _local(self, name, names, which, table=True):
+        """[{name: float32[h][w]}] per local rect of the packed arrays the engine's `name` writes."""
+        rects = self.local_rects()
+        packed = self._store_fields(name, names, which, int(self._L.lbm_local_cells(self._h)), np.float32,
+                                    table=table)
+        return _per_rect(rects, packed)
+
+    def force_history(self, steps: int, every: int, accelerate_first: bool = False):
+        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and sample
+        wall_force() after each chunk.  Returns (samples, av_vels): samples is a list of
+        (step, fx, fy, links) with step = steps done so far, av_vels the float32[steps]
+        concatenation of the chunks' average velocities.  accelerate_first applies to the
+        first chunk only.  In bitwise mode the lattice and av_vels equal those of one
+        run_steps(steps).  In tolerance mode a chunked run differs from an unchunked one
+        in the last bits: the steps of a chunk that do not fill a fused launch run as
+        remainder launches, and remainder launches are bitwise."""
+        return self._stat_history(steps, every, accelerate_first, self.wall_force)
+
+    def gradient_history(self, steps: int, every: int, accelerate_first: bool = False):
+        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and sample
+        gradient_stats() after each chunk.  Returns (samples, av_vels): samples is a list of
+        (step, sum_w2, sum_s2, max_w, max_div) with step = steps done so far, av_vels the
+        float32[steps] concatenation of the chunks' average velocities.  Chunking behaves
+        as in force_history."""
+        return self._stat_history(steps, every, accelerate_first, self.gradient_stats)
+
+    def strain_history(self, steps: int, every: int, accelerate_first: bool = False):
+        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and sample
+        strain_stats() after each chunk.  Returns (samples, av_vels): samples is a list of
+        (step, sum_s2, max_strain, wall_cells, sum_wall_strain, max_wall_strain), av_vels the
+        float32[steps] concatenation of the chunks' average velocities.  Chunking behaves
+        as in force_history."""
+        return self._stat_history(steps, every, accelerate_first, self.strain_stats)
+
+    def run_averaged(self, steps: int, every: int, accelerate_first: bool = False):
+        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and
+        avg_sample() after each chunk (avg_begin first).  Returns the float32[steps]
+        concatenation of the chunks' average velocities.  accelerate_first applies to the
+        first chunk only.  In bitwise mode the lattice and av_vels equal those of one
+        run_steps(steps).  In tolerance mode a chunked run differs from an unchunked one
+        in the last bits: the steps of a chunk that do not fill a fused launch run as
+        remainder launches, and remainder launches are bitwise."""
+        return self._chunks(steps, every, accelerate_first, True, lambda n, done: self.avg_sample())
+
+    def strain_rate_local(self, which=None):
+        """[{name: float32[h][w]}] per local rect (local_rects() order; lbm_store_stress_local)."""
+        return self._local("store_stress_local", STRESS_FIELDS, _select(STRESS_FIELDS, which, "strain-rate fields"))
+
+    def gradients_local(self, which=None):
+        """[{name: float32[h][w]}] per local rect (local_rects() order; lbm_store_gradients_local)."""
+        return self._local("store_gradients_local", GRAD_FIELDS, _select(GRAD_FIELDS, which, "gradient fields"))
 
     def load_cells(self, cells: np.ndarray) -> None:
         c = np.ascontiguousarray(cells, dtype=np.float32)
         if c.size != self.params.nx * self.params.ny * Q:
             raise ValueError("cells must be AoS float32[ny][nx][9]")
-        self._check(self._L.lbm_load_cells(self._h, _f32(c)))
+        self._check(self._L.lbm_load_cells(self._h, _ptr(c)))
 
     def init_equilibrium(self) -> None:
         self._check(self._L.lbm_init_equilibrium(self._h))
@@ -1055,7 +1000,7 @@ class Engine(_WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
         n_av = int(self.params.max_iters if n_av is None else n_av)
         out = np.zeros((self.params.ny, self.params.nx, Q), np.float32) if cells else None
         av = np.zeros(max(n_av, 1), np.float32)
-        self._check(self._L.lbm_store(self._h, _f32(out) if cells else None, _f32(av), n_av))
+        self._check(self._L.lbm_store(self._h, _ptr(out) if cells else None, _ptr(av), n_av))
         return out, av[:n_av]
 
     def load_cells_local(self, blocks) -> None:
@@ -1069,7 +1014,7 @@ class Engine(_WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
                 raise ValueError(f"block shape {np.shape(b)} != {(h, w, Q)}")
         packed = np.ascontiguousarray(np.concatenate([np.asarray(b, np.float32).reshape(-1) for b in blocks]))
         assert packed.size == int(self._L.lbm_local_cells(self._h)) * Q
-        self._check(self._L.lbm_load_cells_local(self._h, _f32(packed)))
+        self._check(self._L.lbm_load_cells_local(self._h, _ptr(packed)))
 
     def store_local(self, cells: bool = True, n_av: int | None = None):
         """Returns ([AoS float32[h][w][9] per local rect] or None, av_vels float32[n_av])."""
@@ -1077,46 +1022,20 @@ class Engine(_WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
         rects = self.local_rects()
         packed = np.zeros(int(self._L.lbm_local_cells(self._h)) * Q, np.float32) if cells else None
         av = np.zeros(max(n_av, 1), np.float32)
-        self._check(self._L.lbm_store_local(self._h, _f32(packed) if cells else None, _f32(av), n_av))
-        if not cells:
-            return None, av[:n_av]
-        out, off = [], 0
-        for (_, _, w, h) in rects:
-            out.append(packed[off:off + w * h * Q].reshape(h, w, Q))
-            off += w * h * Q
-        return out, av[:n_av]
-
-    @staticmethod
-    def _which(which):
-        which = tuple(which)
-        bad = [n for n in which if n not in FIELDS]
-        if bad or len(set(which)) != len(which):
-            raise ValueError(f"fields are a subset of {FIELDS}, each at most once; got {which}")
-        return which
+        self._check(self._L.lbm_store_local(self._h, _ptr(packed) if cells else None, _ptr(av), n_av))
+        return (_per_rect(rects, packed, Q) if cells else None), av[:n_av]
 
     def fields(self, which=FIELDS):
         """{name: float32[ny][nx]} of the requested macroscopic fields ("ux", "uy",
         "speed", "pressure"), computed on the device from the current lattice
         (lbm_store_fields): the values lio.macroscopic derives from store()'s
         cells, bit for bit.  RCCL: only this rank's rectangle is written."""
-        which = self._which(which)
-        out = {n: np.zeros((self.params.ny, self.params.nx), np.float32) for n in which}
-        self._check(self._L.lbm_store_fields(self._h, *[_f32(out[n]) if n in out else None for n in FIELDS]))
-        return out
+        return self._store_fields("store_fields", FIELDS, _select(FIELDS, which, "fields"), self._shape(), np.float32,
+                                  table=False)
 
     def fields_local(self, which=FIELDS):
         """[{name: float32[h][w]}] per local rect (local_rects() order; lbm_store_fields_local)."""
-        which = self._which(which)
-        rects = self.local_rects()
-        n = int(self._L.lbm_local_cells(self._h))
-        packed = {f: np.zeros(n, np.float32) for f in which}
-        self._check(self._L.lbm_store_fields_local(self._h, *[_f32(packed[f]) if f in packed else None
-                                                              for f in FIELDS]))
-        out, off = [], 0
-        for (_, _, w, h) in rects:
-            out.append({f: packed[f][off:off + w * h].reshape(h, w) for f in which})
-            off += w * h
-        return out
+        return self._local("store_fields_local", FIELDS, _select(FIELDS, which, "fields"), table=False)
 
     def field_stats(self):
         """(mass, max_speed) of this handle's sub-domains (lbm_field_stats): the fp64
@@ -1194,99 +1113,16 @@ class Engine(_WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
         """'bitwise' (every kernel equals the CPU oracle) or 'tolerance' (LBM_FLAG_TOLERANCE collision)."""
         return "tolerance" if int(self._L.lbm_numerics(self._h)) == 1 else "bitwise"
 
-    def close(self) -> None:
-        if self._h:
-            self._L.lbm_destroy(self._h)
-            self._h = ctypes.c_void_p()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Engine3D(_WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
+class Engine3D(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
     """One lbm3d_handle: the D3Q19 extension engine (include/lbm3d_hip.h)."""
 
-    _FORCE_PREFIX = "lbm3d_"
+    _PREFIX = "lbm3d_"
     _AVG_FIELDS = AVG_FIELDS3D
     _GRAD_FIELDS = GRAD_FIELDS3D
     _STRESS_FIELDS = STRESS_FIELDS3D
     _BIN_FIELDS = BIN_FIELDS3D
     _TRACER_FIELDS = TRACER_FIELDS3D
-
-    def strain_rate_box(self, x0: int, y0: int, z0: int, nx: int, ny: int, nz: int, which=None):
-        """{name: float32[nz][ny][nx]} of the cells [x0, x0+nx) x [y0, y0+ny) x [z0, z0+nz)
-        (lbm3d_store_stress_box); a box that is empty or leaves the domain raises LbmError."""
-        which = self._stress_which(which)
-        box = Box3D(int(x0), int(y0), int(z0), int(nx), int(ny), int(nz))
-        out = {n: np.zeros((max(box.nz, 0), max(box.ny, 0), max(box.nx, 0)), np.float32) for n in which}
-        self._check(self._L.lbm3d_store_stress_box(self._h, ctypes.byref(box), self._stress_ptrs(out)))
-        return out
-
-    def strain_history(self, steps: int, every: int):
-        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and sample
-        strain_stats() after each chunk: a list of (step, sum_s2, max_strain, wall_cells,
-        sum_wall_strain, max_wall_strain)."""
-        steps, every = int(steps), int(every)
-        if steps < 0 or every < 1:
-            raise ValueError("steps >= 0 and every >= 1")
-        samples, done = [], 0
-        while done < steps:
-            n = min(every, steps - done)
-            self.run_steps(n)
-            done += n
-            samples.append((done,) + self.strain_stats())
-        return samples
-
-    def gradients_box(self, x0: int, y0: int, z0: int, nx: int, ny: int, nz: int, which=None):
-        """{name: float32[nz][ny][nx]} of the cells [x0, x0+nx) x [y0, y0+ny) x [z0, z0+nz)
-        (lbm3d_store_gradients_box).  The stencils of the box's outer cells still read
-        their periodic neighbours; a box that is empty or leaves the domain raises LbmError."""
-        which = self._grad_which(which)
-        box = Box3D(int(x0), int(y0), int(z0), int(nx), int(ny), int(nz))
-        out = {n: np.zeros((max(box.nz, 0), max(box.ny, 0), max(box.nx, 0)), np.float32) for n in which}
-        self._check(self._L.lbm3d_store_gradients_box(self._h, ctypes.byref(box), self._grad_ptrs(out)))
-        return out
-
-    def gradient_history(self, steps: int, every: int):
-        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and sample
-        gradient_stats() after each chunk: a list of (step, sum_w2, sum_s2, max_w, max_div)."""
-        steps, every = int(steps), int(every)
-        if steps < 0 or every < 1:
-            raise ValueError("steps >= 0 and every >= 1")
-        samples, done = [], 0
-        while done < steps:
-            n = min(every, steps - done)
-            self.run_steps(n)
-            done += n
-            samples.append((done,) + self.gradient_stats())
-        return samples
-
-    def run_averaged(self, steps: int, every: int) -> None:
-        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and
-        avg_sample() after each chunk (avg_begin first).  In bitwise mode the lattice
-        equals that of one run_steps(steps); in tolerance mode a chunked run differs from
-        an unchunked one in the last bits (remainder launches are bitwise)."""
-        steps, every = int(steps), int(every)
-        if steps < 0 or every < 1:
-            raise ValueError("steps >= 0 and every >= 1")
-        done = 0
-        while done < steps:
-            n = min(every, steps - done)
-            self.run_steps(n)
-            done += n
-            self.avg_sample()
-
-    def _force_shape(self):
-        return (self.params.nz, self.params.ny, self.params.nx)
 
     def __init__(self, params, obstacles: np.ndarray, *, parts: int = 1, transport: int = TRANSPORT_LOCAL,
                  rank: int = 0, world: int = 1, devices=None, unique_id: bytes | None = None, flags: int = 0):
@@ -1296,27 +1132,60 @@ class Engine3D(_WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
         obst = np.ascontiguousarray(obstacles, dtype=np.uint8)
         if obst.size != self.params.nx * self.params.ny * self.params.nz:
             raise ValueError("obstacles must have nz*ny*nx entries")
-        cfg = Config()
+        cfg = self._config(devices, unique_id)
         cfg.parts = int(world if transport == TRANSPORT_RCCL else parts)
         cfg.transport = transport
         cfg.flags = int(flags)  # FLAG_TOLERANCE: the two-step passes use the reciprocal collision
         cfg.rank, cfg.world = int(rank), int(world)
-        if devices:
-            self._devs = (ctypes.c_int32 * len(devices))(*devices)
-            cfg.devices = self._devs
-            cfg.num_devices = len(devices)
-        if unique_id is not None:
-            self._uid = (ctypes.c_uint8 * 128).from_buffer_copy(unique_id)
-            cfg.rccl_unique_id = self._uid
-        self._h = ctypes.c_void_p()
-        rc = self._L.lbm3d_create(ctypes.byref(self.params), obst.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                  ctypes.byref(cfg), ctypes.byref(self._h))
-        if rc != LBM_OK:
-            raise LbmError(rc, self._L.lbm3d_last_error(None).decode())
+        self._create("create", obst, cfg)
 
-    def _check(self, rc: int):
-        if rc != LBM_OK:
-            raise LbmError(rc, self._L.lbm3d_last_error(self._h).decode())
+    def _shape(self):
+        return (self.params.nz, self.params.ny, self.params.nx)
+
+    # The three chunked runs below keep their own D3Q19 signatures (no accelerate_first, no av_vels),
+    # so they stay thin wrappers beside Engine's instead of one declaration on the mixins.
+    def gradient_history(self, steps: int, every: int):
+        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and sample
+        gradient_stats() after each chunk: a list of (step, sum_w2, sum_s2, max_w, max_div)."""
+        return self._stat_history(steps, every, False, self.gradient_stats)[0]
+
+    def strain_history(self, steps: int, every: int):
+        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and sample
+        strain_stats() after each chunk: a list of (step, sum_s2, max_strain, wall_cells,
+        sum_wall_strain, max_wall_strain)."""
+        return self._stat_history(steps, every, False, self.strain_stats)[0]
+
+    def run_averaged(self, steps: int, every: int) -> None:
+        """Advance `steps` steps in run_steps(every) chunks (the remainder last) and
+        avg_sample() after each chunk (avg_begin first).  In bitwise mode the lattice
+        equals that of one run_steps(steps); in tolerance mode a chunked run differs from
+        an unchunked one in the last bits (remainder launches are bitwise)."""
+        self._chunks(steps, every, False, False, lambda n, done: self.avg_sample())
+
+    def strain_rate_box(self, x0: int, y0: int, z0: int, nx: int, ny: int, nz: int, which=None):
+        """{name: float32[nz][ny][nx]} of the cells [x0, x0+nx) x [y0, y0+ny) x [z0, z0+nz)
+        (lbm3d_store_stress_box); a box that is empty or leaves the domain raises LbmError."""
+        return self._box("store_stress_box", STRESS_FIELDS3D, _select(STRESS_FIELDS3D, which, "strain-rate fields"),
+                         (x0, y0, z0, nx, ny, nz))
+
+    def gradients_box(self, x0: int, y0: int, z0: int, nx: int, ny: int, nz: int, which=None):
+        """{name: float32[nz][ny][nx]} of the cells [x0, x0+nx) x [y0, y0+ny) x [z0, z0+nz)
+        (lbm3d_store_gradients_box).  The stencils of the box's outer cells still read
+        their periodic neighbours; a box that is empty or leaves the domain raises LbmError."""
+        return self._box("store_gradients_box", GRAD_FIELDS3D, _select(GRAD_FIELDS3D, which, "gradient fields"),
+                         (x0, y0, z0, nx, ny, nz))
+
+    def fields_box(self, x0: int, y0: int, z0: int, nx: int, ny: int, nz: int, which=FIELDS3D):
+        """{name: float32[nz][ny][nx]} of the cells [x0, x0+nx) x [y0, y0+ny) x [z0, z0+nz)
+        (lbm3d_store_fields_box; a plane is a box of extent 1 along its normal).  No
+        periodic wrap: a box that is empty or leaves the domain raises LbmError."""
+        return self._box("store_fields_box", FIELDS3D, _select(FIELDS3D, which, "fields"), (x0, y0, z0, nx, ny, nz),
+                         table=False)
+
+    def _box(self, name, names, which, extent, table=True):
+        box = Box3D(*[int(v) for v in extent])
+        shape = (max(box.nz, 0), max(box.ny, 0), max(box.nx, 0))
+        return self._store_fields(name, names, which, shape, np.float32, ctypes.byref(box), table=table)
 
     def init_equilibrium(self) -> None:
         self._check(self._L.lbm3d_init_equilibrium(self._h))
@@ -1325,7 +1194,7 @@ class Engine3D(_WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
         c = np.ascontiguousarray(cells, dtype=np.float32)
         if c.size != self.params.nx * self.params.ny * self.params.nz * Q3:
             raise ValueError("cells must be AoS float32[nz][ny][nx][19]")
-        self._check(self._L.lbm3d_load_cells(self._h, _f32(c)))
+        self._check(self._L.lbm3d_load_cells(self._h, _ptr(c)))
 
     def run_steps(self, steps: int) -> None:
         self._check(self._L.lbm3d_run_steps(self._h, int(steps)))
@@ -1333,37 +1202,16 @@ class Engine3D(_WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
     def store(self, cells: bool = True, n_av: int = 0):
         out = np.zeros((self.params.nz, self.params.ny, self.params.nx, Q3), np.float32) if cells else None
         av = np.zeros(max(int(n_av), 1), np.float32)
-        self._check(self._L.lbm3d_store(self._h, _f32(out) if cells else None, _f32(av), int(n_av)))
+        self._check(self._L.lbm3d_store(self._h, _ptr(out) if cells else None, _ptr(av), int(n_av)))
         return out, av[:int(n_av)]
-
-    @staticmethod
-    def _which(which):
-        which = tuple(which)
-        bad = [n for n in which if n not in FIELDS3D]
-        if bad or len(set(which)) != len(which):
-            raise ValueError(f"fields are a subset of {FIELDS3D}, each at most once; got {which}")
-        return which
 
     def fields(self, which=FIELDS3D):
         """{name: float32[nz][ny][nx]} of the requested macroscopic fields ("ux", "uy",
         "uz", "speed", "pressure"), computed on the device from the current lattice
         (lbm3d_store_fields): the values lio.macroscopic3d derives from store()'s
         cells, bit for bit.  RCCL: only this rank's planes are written."""
-        which = self._which(which)
-        out = {n: np.zeros((self.params.nz, self.params.ny, self.params.nx), np.float32) for n in which}
-        self._check(self._L.lbm3d_store_fields(self._h, *[_f32(out[n]) if n in out else None for n in FIELDS3D]))
-        return out
-
-    def fields_box(self, x0: int, y0: int, z0: int, nx: int, ny: int, nz: int, which=FIELDS3D):
-        """{name: float32[nz][ny][nx]} of the cells [x0, x0+nx) x [y0, y0+ny) x [z0, z0+nz)
-        (lbm3d_store_fields_box; a plane is a box of extent 1 along its normal).  No
-        periodic wrap: a box that is empty or leaves the domain raises LbmError."""
-        which = self._which(which)
-        box = Box3D(int(x0), int(y0), int(z0), int(nx), int(ny), int(nz))
-        out = {n: np.zeros((max(box.nz, 0), max(box.ny, 0), max(box.nx, 0)), np.float32) for n in which}
-        self._check(self._L.lbm3d_store_fields_box(self._h, ctypes.byref(box),
-                                                   *[_f32(out[n]) if n in out else None for n in FIELDS3D]))
-        return out
+        return self._store_fields("store_fields", FIELDS3D, _select(FIELDS3D, which, "fields"), self._shape(),
+                                  np.float32, table=False)
 
     def field_stats(self):
         """(mass, max_speed) of this handle's slabs (lbm3d_field_stats): the fp64 sum of
@@ -1400,20 +1248,3 @@ class Engine3D(_WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
         nz = (ctypes.c_int32 * 64)()
         self._check(self._L.lbm3d_local_slabs(self._h, z0, nz, 64, ctypes.byref(n)))
         return [(z0[i], nz[i]) for i in range(n.value)]
-
-    def close(self) -> None:
-        if self._h:
-            self._L.lbm3d_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

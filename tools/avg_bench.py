@@ -28,19 +28,15 @@ The measurement runs in a child process under `timeout`, so a hang ends it:
 """
 from __future__ import annotations
 
-import argparse
 import json
 import statistics
-import subprocess
 import sys
-import time
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parents[1]
-sys.path[:0] = [str(ROOT), str(ROOT / "lbm-graphcore_amd")]
+import diag_bench
 
 BYTES = {2: (85.0, 149.0), 3: (141.0, 253.0)}   # per cell and sample: MEAN, MEAN|SECOND
 RECORDED_COPY_TBS = 6.29   # float4 device copy, MI355X (tools/fields_bench.py)
+CLASS = "accumulate_moments"
 
 
 def copy_rate_tbs():
@@ -72,41 +68,17 @@ def copy_rate_tbs():
 def worker(a) -> int:
     import numpy as np
 
-    from lbm_amd import io as lio
-    from lbm_amd import native
-
-    if a.dim == 2:
-        from bench import synthetic_obstacles
-        n = a.n or 8192
-        cells, grid = n * n, f"{n}x{n}"
-        p = lio.Params(n, n, a.steps, 10, 0.1, 0.005, 1.85)
-        e = native.Engine(p, synthetic_obstacles(n, n), flags=native.FLAG_PROFILE)
-        first = ("ux", "uy", "pressure")
-        run = lambda k: e.run_steps(k, accelerate_first=False)   # noqa: E731
-    else:
-        n = a.n or 256
-        cells, grid = n ** 3, f"{n}^3"
-        p = lio.Params3D(n, n, n, a.steps, 0.1, 0.001, 1.85)
-        e = native.Engine3D(p, lio.channel_obstacles3d(n, n, n), devices=[0])
-        first = ("ux", "uy", "uz", "pressure")
-        run = e.run_steps
+    e, run, cells, grid, _ = diag_bench.engine(a)
+    first = ("ux", "uy", "pressure") if a.dim == 2 else ("ux", "uy", "uz", "pressure")
     nv = len(first) - 1
     pairs = [(i, j) for i in range(nv) for j in range(i, nv)] + [(nv, nv)]
-    e.init_equilibrium()
-    run(a.steps)
     copy_tbs = copy_rate_tbs()
     copy_source = "measured live" if copy_tbs is not None else "recorded, not measured in this run"
     copy_tbs = RECORDED_COPY_TBS if copy_tbs is None else copy_tbs
     print(f"avg_bench: {grid}, {a.steps} steps, {a.rounds} rounds, device copy {copy_tbs:.2f} TB/s ({copy_source})",
           flush=True)
 
-    def device_ms():
-        if a.dim != 2:
-            return None
-        k = [k for k in e.profile_summary() if k["name"] == "accumulate_moments"]
-        return k[0]["total_ms"] if k else 0.0
-
-    host_sums = [np.zeros(e._force_shape(), np.float64) for _ in range(len(first) + len(pairs))]
+    host_sums = [np.zeros(e._shape(), np.float64) for _ in range(len(first) + len(pairs))]
 
     def fields_numpy():
         f = e.fields(first)
@@ -116,48 +88,27 @@ def worker(a) -> int:
         for k, (i, j) in enumerate(pairs):
             host_sums[len(first) + k] += s[i] * s[j]
 
-    def timed(call):
-        if a.dim == 2:
-            e.profile_reset()
-        t0 = time.perf_counter()
-        out = call()
-        dt = time.perf_counter() - t0
-        del out
-        return dt, device_ms()
-
     names = ("sample_mean", "sample_mean_second", "fields", "fields_numpy")
-    wall = {k: [] for k in names}
-    dev = {k: [] for k in names[:2]}
-    for r in range(a.rounds + 1):
-        got = {}
+
+    def measure():
         for name, second in (("sample_mean", False), ("sample_mean_second", True)):
             e.avg_begin(second=second)   # allocation and zeroing stay outside the timed call
             e.avg_sample()               # first touch of the fresh accumulators
-            got[name] = timed(e.avg_sample)
-        got["fields"] = timed(lambda: e.fields(first))
-        got["fields_numpy"] = timed(fields_numpy)
-        for name, (dt, ms) in got.items():
-            if r > 0:
-                wall[name].append(dt)
-                if name in dev:
-                    dev[name].append(dt * 1e3 if ms is None else ms)
-            print(f"  round {r} {name:20s} wall {dt * 1e3:10.3f} ms" +
-                  ("" if ms is None or name not in dev else f"   accumulate_moments {ms:8.3f} ms"), flush=True)
+            yield (name, *diag_bench.timed(e, e.avg_sample, (CLASS,)))
+        yield ("fields", *diag_bench.timed(e, lambda: e.fields(first)))
+        yield ("fields_numpy", *diag_bench.timed(e, fields_numpy))
+
+    def line(r, name, dt, ms):
+        return (f"  round {r} {name:20s} wall {dt * 1e3:10.3f} ms" +
+                ("" if ms is None or name not in names[:2] else f"   accumulate_moments {ms.get(CLASS, 0.0):8.3f} ms"))
+
+    got = diag_bench.rounds(a.rounds, measure, line)
     # the sampled run against the plain one (the accumulators of MEAN|SECOND are still allocated)
-    cost = {"run_steps_100": [], "run_averaged_100_every_10": []}
-    for r in range(4):
-        t0 = time.perf_counter()
-        run(100)
-        t1 = time.perf_counter()
-        e.run_averaged(100, 10)
-        t2 = time.perf_counter()
-        if r:
-            cost["run_steps_100"].append(t1 - t0)
-            cost["run_averaged_100_every_10"].append(t2 - t1)
+    plain, hist = diag_bench.history_cost(run, lambda: e.run_averaged(100, 10), 3)
     e.avg_end()
     e.close()
-    med_wall = {k: statistics.median(v) for k, v in wall.items()}
-    med_dev = {k: statistics.median(v) for k, v in dev.items()}
+    med_wall = {k: diag_bench.median_wall(got[k]) for k in names}
+    med_dev = {k: diag_bench.median_device(got[k], CLASS) for k in names[:2]}
     tbs = {k: BYTES[a.dim][i] * cells / (med_dev[k] * 1e-3) / 1e12 for i, k in enumerate(names[:2])}
     rec = {
         "tool": "avg_bench", "grid": grid, "steps": a.steps, "rounds": a.rounds,
@@ -167,7 +118,7 @@ def worker(a) -> int:
         "bytes_per_cell": dict(zip(names[:2], BYTES[a.dim])),
         "accumulate_moments_tbs": {k: round(v, 3) for k, v in tbs.items()},
         "device_copy_tbs": round(copy_tbs, 3), "device_copy_source": copy_source,
-        "run_ms": {k: round(statistics.median(v) * 1e3, 3) for k, v in cost.items()},
+        "run_ms": {"run_steps_100": round(plain * 1e3, 3), "run_averaged_100_every_10": round(hist * 1e3, 3)},
         "sample_faster_than_fields": med_wall["sample_mean_second"] < med_wall["fields"],
     }
     w = rec["wall_ms"]
@@ -183,23 +134,5 @@ def worker(a) -> int:
     return 0 if rec["sample_faster_than_fields"] else 1
 
 
-def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--dim", type=int, default=2, choices=(2, 3))
-    ap.add_argument("--n", type=int, default=0, help="edge length (default 8192 for --dim 2, 256 for --dim 3)")
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--limit", type=int, default=600, help="seconds the measuring child may take")
-    ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
-    a = ap.parse_args()
-    if a.rounds < 1:
-        ap.error("--rounds must be >= 1")
-    if a.worker:
-        return worker(a)
-    cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, str(Path(__file__).resolve()), "--worker", "--dim",
-           str(a.dim), "--n", str(a.n), "--steps", str(a.steps), "--rounds", str(a.rounds)]
-    return subprocess.run(cmd).returncode
-
-
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(diag_bench.main(worker, __file__))

@@ -28,90 +28,43 @@ The measurement runs in a child process under `timeout`, so a hang ends it:
 """
 from __future__ import annotations
 
-import argparse
 import json
 import statistics
-import subprocess
 import sys
-import time
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parents[1]
-sys.path[:0] = [str(ROOT), str(ROOT / "lbm-graphcore_amd")]
+import diag_bench
 
 READ_BYTES = {2: 37.0, 3: 77.0}      # populations and the obstacle byte per cell
 PASS, FOLD, STATS = "binned_sums", "binned_sums fold", "macroscopic_fields stats"
 
 
 def worker(a) -> int:
-    from lbm_amd import io as lio
-    from lbm_amd import native
-
+    e, run, cells, grid, _ = diag_bench.engine(a)
+    n = e.params.nx
     if a.dim == 2:
-        from bench import synthetic_obstacles
-        n = a.n or 8192
-        cells, grid = n * n, f"{n}x{n}"
-        p = lio.Params(n, n, a.steps, 10, 0.1, 0.005, 1.85)
-        e = native.Engine(p, synthetic_obstacles(n, n), flags=native.FLAG_PROFILE)
-        run = lambda k: e.run_steps(k, accelerate_first=False)   # noqa: E731
         shapes = {"profile": (n, 1), "sections": (1, n), "coarse16": (16, 16), "total": (n, n)}
     else:
-        n = a.n or 256
-        cells, grid = n ** 3, f"{n}^3"
-        p = lio.Params3D(n, n, n, a.steps, 0.1, 0.001, 1.85)
-        e = native.Engine3D(p, lio.channel_obstacles3d(n, n, n), devices=[0])
-        run = e.run_steps
         shapes = {"profile": (n, 1, n), "sections": (1, n, n), "coarse16": (16, 16, 16), "total": (n, n, n)}
-    e.init_equilibrium()
-    run(a.steps)
     print(f"binned_bench: {grid}, {a.steps} steps, {a.rounds} rounds", flush=True)
-
-    def device_ms():
-        if a.dim != 2:
-            return {}
-        return {k["name"]: k["total_ms"] for k in e.profile_summary() if k["name"] in (PASS, FOLD, STATS)}
-
-    def timed(call):
-        if a.dim == 2:
-            e.profile_reset()
-        t0 = time.perf_counter()
-        out = call()
-        dt = time.perf_counter() - t0
-        del out
-        return dt, device_ms()
 
     calls = [(f"binned {k}", (lambda b: lambda: e.binned(*b))(b)) for k, b in shapes.items()]
     calls += [("coarse_fields(16)", lambda: e.coarse_fields(16)), ("field_stats", e.field_stats), ("fields", e.fields)]
-    wall = {k: [] for k, _ in calls}
-    dev = {k: {} for k, _ in calls}
-    for r in range(a.rounds + 1):
-        for name, call in calls:
-            dt, ms = timed(call)
-            if r > 0:
-                wall[name].append(dt)
-                for cls, v in ms.items():
-                    dev[name].setdefault(cls, []).append(v)
-            print(f"  round {r} {name:20s} wall {dt * 1e3:10.3f} ms   " +
-                  "  ".join(f"{c} {v:.3f} ms" for c, v in ms.items()), flush=True)
-    cost = {"run_steps_100": [], "binned_history_100_every_10_profile": []}
-    for r in range(3):
-        t0 = time.perf_counter()
-        run(100)
-        t1 = time.perf_counter()
-        e.binned_history(100, 10, *shapes["profile"])
-        t2 = time.perf_counter()
-        if r:
-            cost["run_steps_100"].append(t1 - t0)
-            cost["binned_history_100_every_10_profile"].append(t2 - t1)
+
+    def line(r, name, dt, ms):
+        return (f"  round {r} {name:20s} wall {dt * 1e3:10.3f} ms   " +
+                "  ".join(f"{c} {v:.3f} ms" for c, v in (ms or {}).items()))
+
+    got = diag_bench.rounds(a.rounds, diag_bench.each(e, calls, lambda name: (PASS, FOLD, STATS)), line)
+    plain, hist = diag_bench.history_cost(run, lambda: e.binned_history(100, 10, *shapes["profile"]), 2)
     e.close()
-    med_wall = {k: statistics.median(v) for k, v in wall.items()}
-    med_dev = {k: {c: statistics.median(v) for c, v in d.items()} for k, d in dev.items()}
+    med_wall = {k: diag_bench.median_wall(v) for k, v in got.items()}
+    med_dev = {k: {c: statistics.median(ms[c] for _, ms in v) for c in (v[0][1] or {})} for k, v in got.items()}
     rec = {
         "tool": "binned_bench", "grid": grid, "steps": a.steps, "rounds": a.rounds,
         "wall_ms": {k: round(v * 1e3, 3) for k, v in med_wall.items()},
         "device_ms": {k: {c: round(v, 4) for c, v in d.items()} for k, d in med_dev.items() if d},
         "read_bytes_per_cell": READ_BYTES[a.dim],
-        "run_ms": {k: round(statistics.median(v) * 1e3, 3) for k, v in cost.items()},
+        "run_ms": {"run_steps_100": round(plain * 1e3, 3), "binned_history_100_every_10_profile": round(hist * 1e3, 3)},
         "coarse_faster_than_fields": med_wall["coarse_fields(16)"] < med_wall["fields"],
     }
     if a.dim == 2:
@@ -130,23 +83,5 @@ def worker(a) -> int:
     return 0 if rec["coarse_faster_than_fields"] else 1
 
 
-def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--dim", type=int, default=2, choices=(2, 3))
-    ap.add_argument("--n", type=int, default=0, help="edge length (default 8192 for --dim 2, 256 for --dim 3)")
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--limit", type=int, default=600, help="seconds the measuring child may take")
-    ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
-    a = ap.parse_args()
-    if a.rounds < 1:
-        ap.error("--rounds must be >= 1")
-    if a.worker:
-        return worker(a)
-    cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, str(Path(__file__).resolve()), "--worker", "--dim",
-           str(a.dim), "--n", str(a.n), "--steps", str(a.steps), "--rounds", str(a.rounds)]
-    return subprocess.run(cmd).returncode
-
-
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(diag_bench.main(worker, __file__))

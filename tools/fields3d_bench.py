@@ -21,16 +21,10 @@ The measurement runs in a child process under `timeout`, so a hang ends it:
 """
 from __future__ import annotations
 
-import argparse
 import json
-import statistics
-import subprocess
 import sys
-import time
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parents[1]
-sys.path[:0] = [str(ROOT), str(ROOT / "lbm-graphcore_amd")]
+import diag_bench
 
 
 def worker(a) -> int:
@@ -45,26 +39,15 @@ def worker(a) -> int:
     e.run_steps(a.steps)
     print(f"fields3d_bench: {n}^3, {a.steps} steps, {a.rounds} rounds", flush=True)
 
-    calls = {
-        "store_cells": lambda: e.store(cells=True),
-        "fields_all": lambda: e.fields(),
-        "fields_pressure": lambda: e.fields(("pressure",)),
-        "box_z_slice": lambda: e.fields_box(0, 0, n // 2, n, n, 1),
-        "field_stats": lambda: e.field_stats(),
-    }
-    wall = {k: [] for k in calls}
-    for r in range(a.rounds + 1):   # round 0 warms up (first touch of the staging sizes, clocks)
-        for name, call in calls.items():
-            t0 = time.perf_counter()
-            out = call()
-            dt = time.perf_counter() - t0
-            del out
-            if r > 0:
-                wall[name].append(dt)
-            print(f"  round {r} {name:16s} wall {dt * 1e3:10.2f} ms", flush=True)
+    calls = (("store_cells", lambda: e.store(cells=True)), ("fields_all", lambda: e.fields()),
+             ("fields_pressure", lambda: e.fields(("pressure",))),
+             ("box_z_slice", lambda: e.fields_box(0, 0, n // 2, n, n, 1)), ("field_stats", lambda: e.field_stats()))
+    # round 0 warms up (first touch of the staging sizes, clocks)
+    got = diag_bench.rounds(a.rounds, diag_bench.each(e, calls, lambda name: ()),
+                            lambda r, name, dt, ms: f"  round {r} {name:16s} wall {dt * 1e3:10.2f} ms")
     mass, umax = e.field_stats()
     e.close()
-    med = {k: statistics.median(v) for k, v in wall.items()}
+    med = {k: diag_bench.median_wall(v) for k, v in got.items()}
     rec = {
         "tool": "fields3d_bench", "grid": f"{n}^3", "steps": a.steps, "rounds": a.rounds,
         "wall_ms": {k: round(v * 1e3, 3) for k, v in med.items()},
@@ -82,22 +65,5 @@ def worker(a) -> int:
     return 0 if rec["fields_faster_than_store"] else 1
 
 
-def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--n", type=int, default=256)
-    ap.add_argument("--steps", type=int, default=6)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--limit", type=int, default=600, help="seconds the measuring child may take")
-    ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
-    a = ap.parse_args()
-    if a.rounds < 1:
-        ap.error("--rounds must be >= 1")
-    if a.worker:
-        return worker(a)
-    cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, str(Path(__file__).resolve()), "--worker", "--n",
-           str(a.n), "--steps", str(a.steps), "--rounds", str(a.rounds)]
-    return subprocess.run(cmd).returncode
-
-
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(diag_bench.main(worker, __file__, dim=False, n=256, steps=6))

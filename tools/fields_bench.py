@@ -23,18 +23,13 @@ The measurement runs in a child process under `timeout`, so a hang ends it:
 """
 from __future__ import annotations
 
-import argparse
 import json
-import statistics
-import subprocess
 import sys
-import time
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parents[1]
-sys.path[:0] = [str(ROOT), str(ROOT / "lbm-graphcore_amd")]
+import diag_bench
 
 COPY_RATE_TBS = 6.29   # float4 device copy, MI355X (8.0 TB/s HBM3E spec)
+CLASS = "macroscopic_fields"
 
 
 def worker(a) -> int:
@@ -50,33 +45,15 @@ def worker(a) -> int:
     e.run_steps(a.steps, accelerate_first=True)
     print(f"fields_bench: {nx}x{ny}, {a.steps} steps, kernel {e.kernel_in_use()}, {a.rounds} rounds", flush=True)
 
-    def device_ms():
-        k = [k for k in e.profile_summary() if k["name"] == "macroscopic_fields"]
-        return k[0]["total_ms"] if k else 0.0
-
-    calls = {
-        "store_cells": lambda: e.store(cells=True, n_av=0),
-        "fields_all": lambda: e.fields(),
-        "fields_pressure": lambda: e.fields(("pressure",)),
-    }
-    wall = {k: [] for k in calls}
-    dev = {k: [] for k in calls}
-    for r in range(a.rounds + 1):   # round 0 warms up (first-touch of the staging sizes, clocks)
-        for name, call in calls.items():
-            e.profile_reset()
-            t0 = time.perf_counter()
-            out = call()
-            dt = time.perf_counter() - t0
-            del out
-            if r > 0:
-                wall[name].append(dt)
-                dev[name].append(device_ms())
-            print(f"  round {r} {name:16s} wall {dt * 1e3:10.2f} ms   macroscopic_fields {device_ms():8.3f} ms",
-                  flush=True)
+    calls = (("store_cells", lambda: e.store(cells=True, n_av=0)), ("fields_all", lambda: e.fields()),
+             ("fields_pressure", lambda: e.fields(("pressure",))))
+    # round 0 warms up (first-touch of the staging sizes, clocks)
+    got = diag_bench.rounds(a.rounds, diag_bench.each(e, calls, lambda name: (CLASS,)), lambda r, name, dt, ms: (
+        f"  round {r} {name:16s} wall {dt * 1e3:10.2f} ms   macroscopic_fields {ms.get(CLASS, 0.0):8.3f} ms"))
     mass, umax = e.field_stats()
     e.close()
-    med_wall = {k: statistics.median(v) for k, v in wall.items()}
-    med_dev = {k: statistics.median(v) for k, v in dev.items()}
+    med_wall = {k: diag_bench.median_wall(v) for k, v in got.items()}
+    med_dev = {k: diag_bench.median_device(v, CLASS) for k, v in got.items()}
     rec = {
         "tool": "fields_bench", "grid": f"{nx}x{ny}", "steps": a.steps, "rounds": a.rounds,
         "wall_ms": {k: round(v * 1e3, 3) for k, v in med_wall.items()},
@@ -98,23 +75,6 @@ def worker(a) -> int:
     return 0 if rec["fields_faster_than_store"] else 1
 
 
-def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--n", type=int, default=8192)
-    ap.add_argument("--ny", type=int, default=0)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--limit", type=int, default=300, help="seconds the measuring child may take")
-    ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
-    a = ap.parse_args()
-    if a.rounds < 1:
-        ap.error("--rounds must be >= 1")
-    if a.worker:
-        return worker(a)
-    cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, str(Path(__file__).resolve()), "--worker", "--n",
-           str(a.n), "--ny", str(a.ny), "--steps", str(a.steps), "--rounds", str(a.rounds)]
-    return subprocess.run(cmd).returncode
-
-
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(diag_bench.main(worker, __file__, lambda ap: ap.add_argument("--ny", type=int, default=0),
+                             dim=False, n=8192, limit=300))

@@ -28,18 +28,14 @@ The measurement runs in a child process under `timeout`, so a hang ends it:
 """
 from __future__ import annotations
 
-import argparse
 import json
 import statistics
-import subprocess
 import sys
 import time
-from pathlib import Path
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parents[1]
-sys.path[:0] = [str(ROOT), str(ROOT / "lbm-graphcore_amd")]
+import diag_bench
 
 
 def obstacles2d(nx, ny, kind):
@@ -129,23 +125,14 @@ def case2d(a, kind):
              "field_stats": e.field_stats, "store_numpy": store_numpy}
     wall, dev = timed_rounds(calls, a.rounds, {"store_numpy"}, device_ms, e.profile_reset)
     # force_history(every=10) against plain run_steps, the same number of steps, interleaved
-    hist, plain = [], []
     steps = a.hsteps
-    for r in range(a.rounds + 1):
-        t0 = time.perf_counter()
-        e.run_steps(steps)
-        t1 = time.perf_counter()
-        e.force_history(steps, 10)
-        t2 = time.perf_counter()
-        if r > 0:
-            plain.append(t1 - t0)
-            hist.append(t2 - t1)
-    per_step_us = (statistics.median(hist) - statistics.median(plain)) / steps * 1e6
+    plain, hist = diag_bench.history_cost(e.run_steps, lambda: e.force_history(steps, 10), a.rounds, steps)
+    per_step_us = (hist - plain) / steps * 1e6
     e.close()
     rec = {"tool": "force_bench", "case": f"2d {kind}", "grid": f"{nx}x{ny}", "wall_cells": nwall, "bodies": nbodies,
            "wall_ms": wall, "device_ms": dev, "list_build_s": round(t_build, 3), "set_bodies_s": round(t_bodies, 3),
-           "run_steps_ms": round(statistics.median(plain) * 1e3, 3),
-           "force_history_every10_ms": round(statistics.median(hist) * 1e3, 3), "history_steps": steps,
+           "run_steps_ms": round(plain * 1e3, 3),
+           "force_history_every10_ms": round(hist * 1e3, 3), "history_steps": steps,
            "force_history_added_us_per_step": round(per_step_us, 3)}
     print(json.dumps(rec), flush=True)
     return rec
@@ -204,30 +191,12 @@ def worker(a) -> int:
     return 0 if ok else 1
 
 
-def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--n", type=int, default=8192)
+def more_arguments(ap) -> None:
     ap.add_argument("--n3", type=int, default=256)
-    ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--hsteps", type=int, default=100, help="steps of the force_history comparison")
-    ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--only", choices=("2d", "3d"), default="")
     ap.add_argument("--kind", choices=("sparse", "random"), default="")
-    ap.add_argument("--limit", type=int, default=900, help="seconds the measuring child may take")
-    ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
-    a = ap.parse_args()
-    if a.rounds < 1:
-        ap.error("--rounds must be >= 1")
-    if a.worker:
-        return worker(a)
-    cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, str(Path(__file__).resolve()), "--worker"]
-    for k in ("n", "n3", "steps", "hsteps", "rounds"):
-        cmd += [f"--{k}", str(getattr(a, k))]
-    for k in ("only", "kind"):
-        if getattr(a, k):
-            cmd += [f"--{k}", getattr(a, k)]
-    return subprocess.run(cmd).returncode
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(diag_bench.main(worker, __file__, more_arguments, dim=False, n=8192, limit=900))

@@ -30,67 +30,31 @@ The measurement runs in a child process under `timeout`, so a hang ends it:
 """
 from __future__ import annotations
 
-import argparse
 import json
 import statistics
-import subprocess
 import sys
-import time
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parents[1]
-sys.path[:0] = [str(ROOT), str(ROOT / "lbm-graphcore_amd")]
+import diag_bench
 
 # bytes a point reads per interpolation (4 / 8 cells of Q populations and a map byte) and per call
 CELL_BYTES = {2: 4 * 37.0, 3: 8 * 77.0}
 POS_BYTES = {2: 16.0, 3: 24.0}
+CLASSES = {"advance_heun": "advance_tracers", "sample": "sample_tracers"}
 
 
 def worker(a) -> int:
     import numpy as np
 
     from lbm_amd import io as lio
-    from lbm_amd import native
 
-    if a.dim == 2:
-        from bench import synthetic_obstacles
-        n = a.n or 8192
-        grid, extent = f"{n}x{n}", (n, n)
-        p = lio.Params(n, n, a.steps, 10, 0.1, 0.005, 1.85)
-        e = native.Engine(p, synthetic_obstacles(n, n), flags=native.FLAG_PROFILE)
-        vel = ("ux", "uy")
-        run = lambda k: e.run_steps(k, accelerate_first=False)   # noqa: E731
-        advance_np = lio.tracer_advance
-    else:
-        n = a.n or 256
-        grid, extent = f"{n}^3", (n, n, n)
-        p = lio.Params3D(n, n, n, a.steps, 0.1, 0.001, 1.85)
-        e = native.Engine3D(p, lio.channel_obstacles3d(n, n, n), devices=[0])
-        vel = ("ux", "uy", "uz")
-        run = e.run_steps
-        advance_np = lio.tracer_advance3d
-    e.init_equilibrium()
-    run(a.steps)
+    e, run, _, grid, _ = diag_bench.engine(a)
+    extent = (e.params.nx,) * a.dim
+    vel = ("ux", "uy") if a.dim == 2 else ("ux", "uy", "uz")
+    advance_np = lio.tracer_advance if a.dim == 2 else lio.tracer_advance3d
     counts = [int(c) for c in a.points.split(",")]
     print(f"tracer_bench: {grid}, {a.steps} steps, {a.rounds} rounds, points {counts}", flush=True)
 
-    def device_ms(cls):
-        if a.dim != 2:
-            return None
-        k = [k for k in e.profile_summary() if k["name"] == cls]
-        return k[0]["total_ms"] if k else 0.0
-
-    def timed(call, cls=None):
-        if a.dim == 2:
-            e.profile_reset()
-        t0 = time.perf_counter()
-        out = call()
-        dt = time.perf_counter() - t0
-        del out
-        return dt, (device_ms(cls) if cls else None)
-
     rng = np.random.default_rng(1)
-    names = ("advance_heun", "sample", "fields", "fields_numpy_heun")
     rec = {"tool": "tracer_bench", "grid": grid, "steps": a.steps, "rounds": a.rounds,
            "device_time_source": "profile_summary" if a.dim == 2 else "wall time of the blocking call",
            "bytes_per_point": {"advance_heun": 2 * CELL_BYTES[a.dim] + 2 * POS_BYTES[a.dim],
@@ -99,30 +63,22 @@ def worker(a) -> int:
     for npts in counts:
         pos = [rng.random(npts) * ext for ext in extent]
         e.tracers_begin(*pos)
-        wall = {k: [] for k in names}
-        dev = {k: [] for k in names[:2]}
 
         def fields_numpy():
             f = e.fields(vel)
             return advance_np(*[f[k] for k in vel], *pos, 1.0, "heun")
 
-        for r in range(a.rounds + 1):
-            got = {
-                "advance_heun": timed(lambda: e.tracers_advance(1, "heun"), "advance_tracers"),
-                "sample": timed(e.tracer_sample, "sample_tracers"),
-                "fields": timed(lambda: e.fields(vel)),
-                "fields_numpy_heun": timed(fields_numpy),
-            }
-            for name, (dt, ms) in got.items():
-                if r > 0:
-                    wall[name].append(dt)
-                    if name in dev:
-                        dev[name].append(dt * 1e3 if ms is None else ms)
-                print(f"  n {npts:9d} round {r} {name:18s} wall {dt * 1e3:10.3f} ms" +
-                      ("" if ms is None else f"   device {ms:9.4f} ms"), flush=True)
+        calls = (("advance_heun", lambda: e.tracers_advance(1, "heun")), ("sample", e.tracer_sample),
+                 ("fields", lambda: e.fields(vel)), ("fields_numpy_heun", fields_numpy))
+
+        def line(r, name, dt, ms):
+            return (f"  n {npts:9d} round {r} {name:18s} wall {dt * 1e3:10.3f} ms" +
+                    ("" if ms is None or name not in CLASSES else f"   device {ms.get(CLASSES[name], 0.0):9.4f} ms"))
+
+        got = diag_bench.rounds(a.rounds, diag_bench.each(e, calls, lambda name: (CLASSES.get(name),)), line)
         e.tracers_end()
-        w = {k: statistics.median(v) * 1e3 for k, v in wall.items()}
-        d = {k: statistics.median(v) for k, v in dev.items()}
+        w = {k: diag_bench.median_wall(v) * 1e3 for k, v in got.items()}
+        d = {k: diag_bench.median_device(got[k], c) for k, c in CLASSES.items()}
         rec["points"][str(npts)] = {
             "wall_ms": {k: round(v, 3) for k, v in w.items()},
             "device_ms": {k: round(v, 4) for k, v in d.items()},
@@ -154,24 +110,6 @@ def worker(a) -> int:
     return 0 if rec["advance_faster_than_fields"] else 1
 
 
-def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--dim", type=int, default=2, choices=(2, 3))
-    ap.add_argument("--n", type=int, default=0, help="edge length (default 8192 for --dim 2, 256 for --dim 3)")
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--points", default="100000,1000000,10000000")
-    ap.add_argument("--limit", type=int, default=600, help="seconds the measuring child may take")
-    ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
-    a = ap.parse_args()
-    if a.rounds < 1:
-        ap.error("--rounds must be >= 1")
-    if a.worker:
-        return worker(a)
-    cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, str(Path(__file__).resolve()), "--worker", "--dim",
-           str(a.dim), "--n", str(a.n), "--steps", str(a.steps), "--rounds", str(a.rounds), "--points", a.points]
-    return subprocess.run(cmd).returncode
-
-
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(diag_bench.main(worker, __file__,
+                             lambda ap: ap.add_argument("--points", default="100000,1000000,10000000")))
