@@ -20,6 +20,14 @@
 // stores); no MFMA.  Arithmetic in IEEE fp32 evaluated in the order of
 // oracle/lbm_oracle3d.c (-ffp-contract=off, correctly rounded / and sqrt), so
 // the lattice is bitwise equal to the CPU restatement.
+//
+// Every kernel is built from the same pieces, each written once: the cell
+// (rebound3 for an obstacle; cell3d, or cell3dt in tolerance mode, for fluid),
+// the block fold of |u| (fold_levels) and, for the two- and three-step
+// passes, a level's LDS publish, pull gather and reload (publish3, gather3,
+// reload3).  The kernels differ in how they pull and in how many steps a pass
+// over the lattice makes: step3d (one cell per lane), step3d_pair (a column
+// pair per lane), step3d_two and step3d_three (two and three steps per pass).
 
 #include <hip/hip_runtime.h>
 
@@ -36,132 +44,35 @@
 namespace lbm {
 
 constexpr int B3X = 64, B3Y = 4;  // block: 64 x-columns (one wave) x 4 rows
+static_assert(B3X == 64, "the one-step kernels fold a row as one wave");
 
-__global__ __launch_bounds__(B3X * B3Y) void step3d(Step3Args a) {
-    __shared__ float lds[B3X * B3Y / 64];
-    const int x = blockIdx.x * B3X + threadIdx.x;
-    const int y = blockIdx.y * B3Y + threadIdx.y;
-    const int z = a.z0 + blockIdx.z;
-    float usum = 0.f;
-    if (x < a.nx && y < a.ny) {
-        const int xw = x == 0 ? a.nx - 1 : x - 1, xe = x == a.nx - 1 ? 0 : x + 1;
-        const int ys = y == 0 ? a.ny - 1 : y - 1, yn = y == a.ny - 1 ? 0 : y + 1;
-        const long long PL = a.PL, KS = a.KS;
-        const int px = a.px;
-        // pulled populations s_k = f_k(x - cx, y - cy, z - cz)
-        const float *p0 = a.fin + (long long)z * PL;  // plane z
-        const float *pm = p0 - PL;                     // plane z-1 (c_z = +1 pulls from below)
-        const float *pp = p0 + PL;                     // plane z+1
-        const long long ry = (long long)y * px, rs = (long long)ys * px, rn = (long long)yn * px;
-        float s[Q3];
-        s[0] = p0[0 * KS + ry + x];
-        s[1] = p0[1 * KS + ry + xw];
-        s[2] = p0[2 * KS + ry + xe];
-        s[3] = p0[3 * KS + rs + x];
-        s[4] = p0[4 * KS + rn + x];
-        s[5] = p0[5 * KS + rs + xw];
-        s[6] = p0[6 * KS + rn + xe];
-        s[7] = p0[7 * KS + rn + xw];
-        s[8] = p0[8 * KS + rs + xe];
-        s[9] = pm[9 * KS + ry + x];
-        s[10] = pm[10 * KS + ry + xw];
-        s[11] = pm[11 * KS + ry + xe];
-        s[12] = pm[12 * KS + rs + x];
-        s[13] = pm[13 * KS + rn + x];
-        s[14] = pp[14 * KS + ry + x];
-        s[15] = pp[15 * KS + ry + xe];
-        s[16] = pp[16 * KS + ry + xw];
-        s[17] = pp[17 * KS + rn + x];
-        s[18] = pp[18 * KS + rs + x];
-        float o[Q3];
-        const bool ob = a.obst[((long long)blockIdx.z * a.ny + y) * a.nx + x] != 0;
-        if (ob) {  // bounce-back: out_k = s_opp(k)
-            o[0] = s[0];
-            o[1] = s[2];
-            o[2] = s[1];
-            o[3] = s[4];
-            o[4] = s[3];
-            o[5] = s[6];
-            o[6] = s[5];
-            o[7] = s[8];
-            o[8] = s[7];
+// bounce-back of an obstacle cell: out_k = s_opp(k)
+__device__ __forceinline__ void rebound3(const float (&s)[Q3], float (&o)[Q3]) {
+    o[0] = s[0];
+    o[1] = s[2];
+    o[2] = s[1];
+    o[3] = s[4];
+    o[4] = s[3];
+    o[5] = s[6];
+    o[6] = s[5];
+    o[7] = s[8];
+    o[8] = s[7];
 #pragma unroll
-            for (int i = 0; i < 5; ++i) {
-                o[9 + i] = s[14 + i];
-                o[14 + i] = s[9 + i];
-            }
-        } else {
-            const float rho = s[0] + s[1] + s[2] + s[3] + s[4] + s[5] + s[6] + s[7] + s[8] + s[9] + s[10] + s[11] +
-                              s[12] + s[13] + s[14] + s[15] + s[16] + s[17] + s[18];
-            const float ux = ((s[1] + s[5] + s[7] + s[10] + s[16]) - (s[2] + s[6] + s[8] + s[11] + s[15])) / rho;
-            const float uy = ((s[3] + s[5] + s[8] + s[12] + s[18]) - (s[4] + s[6] + s[7] + s[13] + s[17])) / rho;
-            const float uz = ((s[9] + s[10] + s[11] + s[12] + s[13]) - (s[14] + s[15] + s[16] + s[17] + s[18])) / rho;
-            const float usq = ux * ux + uy * uy + uz * uz;
-            const float c = 1.00f - usq * 1.50f;
-            const float ld0 = rho / 3.00f * a.omega;
-            const float ld1 = rho / 18.00f * a.omega;
-            const float ld2 = rho / 36.00f * a.omega;
-            const float pxy = ux + uy, mxy = ux - uy, pxz = ux + uz, mxz = -ux + uz, pyz = uy + uz, myz = -uy + uz;
-            const float e[Q3] = {0.f, ux, -ux, uy, -uy, pxy, -pxy, mxy, -mxy, uz, pxz, mxz, pyz, myz,
-                                 -uz, -pxz, -mxz, -pyz, -myz};
-            const float omo = a.omo;
-            o[0] = s[0] * omo + ld0 * c;
-#pragma unroll
-            for (int k = 1; k < Q3; ++k) {
-                const float ld = (k <= 4 || k == 9 || k == 14) ? ld1 : ld2;
-                o[k] = s[k] * omo + ld * ((4.50f * e[k]) * (2.00f / 3.00f + e[k]) + c);
-            }
-            const float w1 = a.w1, w2 = a.w2;
-            o[1] = o[1] + w1;
-            o[2] = o[2] - w1;
-            o[5] = o[5] + w2;
-            o[6] = o[6] - w2;
-            o[7] = o[7] + w2;
-            o[8] = o[8] - w2;
-            o[10] = o[10] + w2;
-            o[11] = o[11] - w2;
-            o[15] = o[15] - w2;
-            o[16] = o[16] + w2;
-            usum = sqrtf(usq);
-        }
-        float *d = a.fout + (long long)z * PL + ry + x;
-#pragma unroll
-        for (int k = 0; k < Q3; ++k) d[k * KS] = o[k];
-    }
-    // block partial in a fixed order (waves in threadIdx order)
-    float v = usum;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    const int t = threadIdx.y * B3X + threadIdx.x;
-    if ((t & 63) == 0) lds[t >> 6] = v;
-    __syncthreads();
-    if (t == 0) {
-        float b = lds[0];
-#pragma unroll
-        for (int i = 1; i < B3X * B3Y / 64; ++i) b += lds[i];
-        a.partials[((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = b;
+    for (int i = 0; i < 5; ++i) {
+        o[9 + i] = s[14 + i];
+        o[14 + i] = s[9 + i];
     }
 }
 
 // One D3Q19 cell: pulled populations s -> outputs o (the order of
-// oracle/lbm_oracle3d.c cell3d); returns |u| (0 for an obstacle).
+// oracle/lbm_oracle3d.c cell3d); returns |u| (0 for an obstacle).  |u| feeds
+// av_vels only: by v_sqrt_f32 (<= 1 ulp, as lbm_packed.hpp sqrt_av), or
+// (IEEE_ROOT, the one-cell kernel) correctly rounded.
+template <bool IEEE_ROOT = false>
 __device__ __forceinline__ float cell3d(const float (&s)[Q3], float (&o)[Q3], bool ob, float omega, float omo,
                                         float w1, float w2) {
     if (ob) {
-        o[0] = s[0];
-        o[1] = s[2];
-        o[2] = s[1];
-        o[3] = s[4];
-        o[4] = s[3];
-        o[5] = s[6];
-        o[6] = s[5];
-        o[7] = s[8];
-        o[8] = s[7];
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            o[9 + i] = s[14 + i];
-            o[14 + i] = s[9 + i];
-        }
+        rebound3(s, o);
         return 0.f;
     }
     const float rho = s[0] + s[1] + s[2] + s[3] + s[4] + s[5] + s[6] + s[7] + s[8] + s[9] + s[10] + s[11] + s[12] +
@@ -207,7 +118,7 @@ __device__ __forceinline__ float cell3d(const float (&s)[Q3], float (&o)[Q3], bo
     o[11] = o[11] - w2;
     o[15] = o[15] - w2;
     o[16] = o[16] + w2;
-    return __builtin_amdgcn_sqrtf(usq);  // |u| feeds av_vels only (<= 1 ulp, as lbm_packed.hpp sqrt_av)
+    return IEEE_ROOT ? sqrtf(usq) : __builtin_amdgcn_sqrtf(usq);
 }
 
 // LBM_FLAG_TOLERANCE form of cell3d (the 2-D collide2t's reassociation in
@@ -222,20 +133,7 @@ __device__ __forceinline__ float cell3d(const float (&s)[Q3], float (&o)[Q3], bo
 __device__ __forceinline__ float cell3dt(const float (&s)[Q3], float (&o)[Q3], bool ob, float omo, float k0, float k1,
                                          float k2, float w1, float w2) {
     if (ob) {
-        o[0] = s[0];
-        o[1] = s[2];
-        o[2] = s[1];
-        o[3] = s[4];
-        o[4] = s[3];
-        o[5] = s[6];
-        o[6] = s[5];
-        o[7] = s[8];
-        o[8] = s[7];
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            o[9 + i] = s[14 + i];
-            o[14 + i] = s[9 + i];
-        }
+        rebound3(s, o);
         return 0.f;
     }
     const float ax = s[1] + s[5] + s[7] + s[10] + s[16], bx = s[2] + s[6] + s[8] + s[11] + s[15];
@@ -273,6 +171,91 @@ __device__ __forceinline__ float cell3dt(const float (&s)[Q3], float (&o)[Q3], b
     return __builtin_amdgcn_sqrtf(h) * (1.00f / 3.00f);  // |u|, av_vels only
 }
 
+// Block sums of the per-thread u[0 .. N) of a block of NW waves, in a fixed
+// order: lanes by __shfl_down 32..1, then the waves in row order by thread 0,
+// which writes level l's sum to partials[l * nblocks + blk].  lane / w: the
+// thread's lane and wave (row).  Every thread of the block must reach it (it
+// holds a barrier).
+template <int N, int NW>
+__device__ __forceinline__ void fold_levels(float (&u)[N], float (&red)[N][NW], int lane, int w, float *partials,
+                                            int nblocks, long long blk) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int l = 0; l < N; ++l) u[l] += __shfl_down(u[l], off, 64);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int l = 0; l < N; ++l) red[l][w] = u[l];
+    }
+    __syncthreads();
+    if (lane == 0 && w == 0) {
+#pragma unroll
+        for (int l = 0; l < N; ++l) {
+            float b = red[l][0];
+#pragma unroll
+            for (int i = 1; i < NW; ++i) b += red[l][i];
+            partials[l * nblocks + blk] = b;
+        }
+    }
+}
+
+// the one-step kernels' fold: one level, the block's partial at its grid index
+__device__ __forceinline__ void fold_block3(float usum, float (&red)[1][B3Y], float *partials) {
+    float u[1] = {usum};
+    fold_levels(u, red, threadIdx.x, threadIdx.y, partials, 0,
+                ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
+}
+
+// One cell per lane, one plane per block: the kernel of odd nx (LBM3D_PAIR=0
+// forces it).  Same cell3d arithmetic as every other kernel; its |u| keeps
+// the correctly rounded root.
+__global__ __launch_bounds__(B3X * B3Y) void step3d(Step3Args a) {
+    __shared__ float red[1][B3Y];
+    const int x = blockIdx.x * B3X + threadIdx.x;
+    const int y = blockIdx.y * B3Y + threadIdx.y;
+    const int z = a.z0 + blockIdx.z;
+    float usum = 0.f;
+    if (x < a.nx && y < a.ny) {
+        const int xw = x == 0 ? a.nx - 1 : x - 1, xe = x == a.nx - 1 ? 0 : x + 1;
+        const int ys = y == 0 ? a.ny - 1 : y - 1, yn = y == a.ny - 1 ? 0 : y + 1;
+        const long long PL = a.PL, KS = a.KS;
+        const int px = a.px;
+        // pulled populations s_k = f_k(x - cx, y - cy, z - cz)
+        const float *p0 = a.fin + (long long)z * PL;  // plane z
+        const float *pm = p0 - PL;                     // plane z-1 (c_z = +1 pulls from below)
+        const float *pp = p0 + PL;                     // plane z+1
+        const long long ry = (long long)y * px, rs = (long long)ys * px, rn = (long long)yn * px;
+        float s[Q3];
+        s[0] = p0[0 * KS + ry + x];
+        s[1] = p0[1 * KS + ry + xw];
+        s[2] = p0[2 * KS + ry + xe];
+        s[3] = p0[3 * KS + rs + x];
+        s[4] = p0[4 * KS + rn + x];
+        s[5] = p0[5 * KS + rs + xw];
+        s[6] = p0[6 * KS + rn + xe];
+        s[7] = p0[7 * KS + rn + xw];
+        s[8] = p0[8 * KS + rs + xe];
+        s[9] = pm[9 * KS + ry + x];
+        s[10] = pm[10 * KS + ry + xw];
+        s[11] = pm[11 * KS + ry + xe];
+        s[12] = pm[12 * KS + rs + x];
+        s[13] = pm[13 * KS + rn + x];
+        s[14] = pp[14 * KS + ry + x];
+        s[15] = pp[15 * KS + ry + xe];
+        s[16] = pp[16 * KS + ry + xw];
+        s[17] = pp[17 * KS + rn + x];
+        s[18] = pp[18 * KS + rs + x];
+        float o[Q3];
+        const bool ob = a.obst[((long long)blockIdx.z * a.ny + y) * a.nx + x] != 0;
+        usum = cell3d<true>(s, o, ob, a.omega, a.omo, a.w1, a.w2);
+        float *d = a.fout + (long long)z * PL + ry + x;
+#pragma unroll
+        for (int k = 0; k < Q3; ++k) d[k * KS] = o[k];
+    }
+    fold_block3(usum, red, a.partials);
+}
+
 // Two cells per lane (a column pair, nx even): every load and store is a
 // float2 (512 B per wave instruction instead of 256); the x-shifted pulls
 // take the neighbour column from the adjacent lane by DPP, and the first /
@@ -281,7 +264,7 @@ __device__ __forceinline__ float cell3dt(const float (&s)[Q3], float (&o)[Q3], b
 // ZB times fewer.  Bitwise equal to step3d (same cell3d arithmetic).
 template <int ZB, bool NT>
 __global__ __launch_bounds__(B3X * B3Y) void step3d_pair(Step3Args a, int planes) {
-    __shared__ float lds[B3X * B3Y / 64];
+    __shared__ float red[1][B3Y];
     const int lane = threadIdx.x;
     const int xa = blockIdx.x * (2 * B3X) + 2 * lane;
     const int y = blockIdx.y * B3Y + threadIdx.y;
@@ -361,28 +344,17 @@ __global__ __launch_bounds__(B3X * B3Y) void step3d_pair(Step3Args a, int planes
             }
         }
     }
-    float v = usum;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    const int t = threadIdx.y * B3X + threadIdx.x;
-    if ((t & 63) == 0) lds[t >> 6] = v;
-    __syncthreads();
-    if (t == 0) {
-        float b = lds[0];
-#pragma unroll
-        for (int i = 1; i < B3X * B3Y / 64; ++i) b += lds[i];
-        a.partials[((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = b;
-    }
+    fold_block3(usum, red, a.partials);
 }
 
 // ---------------------------------------------------------------------------
 // Two time steps per pass over the lattice (one slab, z periodic): 2.5-D
 // temporal blocking.  A block of 64 columns (one wave, one column per lane) x
-// TH rows (one wave per row) walks a segment of z planes; as input plane j
+// 12 rows (one wave per row) walks a segment of z planes; as input plane j
 // arrives (step t, 19 coalesced loads per lane), level 1 computes plane j-1 at
 // t+1 and level 2 computes plane j-2 at t+2 from level 1's planes, so the
-// lattice crosses HBM once per two steps.  Owned outputs: the inner 60 x
-// (TH - 4) cells (a two-cell ring in x and y is recomputed).
+// lattice crosses HBM once per two steps.  Owned outputs: the inner 60 x 8
+// cells (a two-cell ring in x and y is recomputed).
 // Pulls, per level, for the centre plane z (input plane z+1 just arrived):
 //   own row, x +- 1 by DPP:   speeds 0,1,2 of plane z, 9,10,11 of plane z-1
 //                             (registers kept from earlier iterations),
@@ -392,32 +364,25 @@ __global__ __launch_bounds__(B3X * B3Y) void step3d_pair(Step3Args a, int planes
 //                             12,13 of plane z-1 (ring of 3), 17,18 of z+1.
 // Two barriers per iteration (one per level) order every slot's writes and
 // reads (each slot is rewritten only after the barrier that follows its last
-// read).  Algorithmic traffic per cell update: (19 loads x 64 TH / (60 (TH-4))
-// + 19 stores) x 4 B / 2 = 98.8 B at TH = 12, 92.3 B at TH = 16, instead of
-// 152.  Same cell3d arithmetic: bitwise equal to the one-step kernels.
+// read).  Algorithmic traffic per cell update: (19 loads x 64 x 12 / (60 x 8)
+// + 19 stores) x 4 B / 2 = 98.8 B instead of 152.  Same cell3d arithmetic:
+// bitwise equal to the one-step kernels.
 // ---------------------------------------------------------------------------
-// TH = rows per block (waves), a template parameter (LBM3D_TH): two levels of
-// 14 plane slots of 64 x TH floats take 7 x TH KB of LDS (TH <= 16: one
-// block of 16 waves per CU, 4 per SIMD).
-// SKIP: a wave whose row no level-2 (level-1) cell depends on skips that
-// level's collision (rows 0 and TH-1 at level 1; rows 0, 1, TH-2, TH-1 at
-// level 2) -- it still writes and reads its LDS slots and barriers, and the
-// skipped values are never read (level 2 of rows 2 .. TH-3 pulls from level-1
-// rows 1 .. TH-2).
-constexpr int T3W = 64;
-constexpr int T3OX = T3W - 4;  // owned columns
+// The block of both passes: 64 columns x 12 rows (waves).  A level's LDS is 14
+// plane slots of 64 x 12 floats = 42 KB: two levels 84 KB, three 126 KB (one
+// block per CU, three waves per SIMD).  Blocks of 14-16 rows, a dead-row skip
+// in the two-step pass and two prefetched planes were measured and removed
+// (profiles/r02/d3q19/ab_two_th_skip_pd.log, profiles/r03/d3q19/ab_pd.log).
+constexpr int T3W = 64;             // columns (lanes) per block
+constexpr int T3TH = 12;            // rows (waves) per block
+constexpr int T3C = T3W * T3TH;     // cells per plane slot
 // Z (speeds 3..8 of the newest plane) is single-buffered: each thread reads
 // its six y +- 1 pulls right after the barrier that publishes them and keeps
 // them in registers (zr) until the next iteration, when that plane is the
-// centre plane -- 14 slots per level instead of 20 (round 3), so blocks of
-// 16 rows fit (owned 60 x 12 of 64 x 16 loaded: 92 B per update instead of
-// 98.8 for 12 rows).
-template <int TH>
-struct T3 {
-    static constexpr int C = T3W * TH;                    // cells per plane slot
-    static constexpr int LDS = (2 + 6 + 3 * 2) * C;       // floats per level: M, Z[6], P[3][2]
-    static constexpr int OY = TH - 4;                     // owned rows
-};
+// centre plane -- 14 slots per level instead of 20.
+constexpr int T3LDS = (2 + 6 + 3 * 2) * T3C;         // floats per level: M[2], Z[6], P[3][2]
+constexpr int T3OX = T3W - 4, T3OY = T3TH - 4;       // owned columns / rows of the two-step pass
+constexpr int T3OX3 = T3W - 6, T3OY3 = T3TH - 6;     // ... of the three-step pass
 
 // XCD-aware block order for the multi-step passes (as the 2-D stream
 // kernel's xcd_remap, lbm_device.hpp): the hardware deals workgroups to the
@@ -438,61 +403,94 @@ __device__ __forceinline__ Blk3 blk3_remap() {
     return Blk3{l - yz * (int)gridDim.x, yz % (int)gridDim.y, yz / (int)gridDim.y};
 }
 
-// One level for centre plane jz - 1, input plane jz (in).  Must be reached by
-// every thread of the block (it holds a barrier).  live (wave-uniform): some
-// later level or output needs this row's result.
-template <int TH, bool TOL>
-__device__ __forceinline__ float level3(const float (&in)[Q3], float (&out)[Q3], float *lds, int jz, float (&r0)[3],
-                                        float (&r9a)[3], float (&r9b)[3], float (&zr)[6], int lane, int wy, bool ob,
-                                        bool live, const Two3Args &a) {
-    constexpr int T3C = T3<TH>::C;
-    float *M = lds, *Z = lds + 2 * T3C, *P = lds + 8 * T3C;
-    const int c = wy * T3W + lane;
-    const int pw = ((jz % 3) + 3) % 3;  // P slot of plane jz
-    M[c] = in[17];
-    M[T3C + c] = in[18];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) Z[i * T3C + c] = in[3 + i];
-    P[(pw * 2) * T3C + c] = in[12];
-    P[(pw * 2 + 1) * T3C + c] = in[13];
-    __syncthreads();
-    const int wm = max(wy - 1, 0) * T3W, wp = min(wy + 1, TH - 1) * T3W;
+// per-thread LDS offsets (floats) of a level's slots, loop-invariant; the
+// neighbours of the block's edge rows and lanes are clamped (those cells are
+// in the recomputed ring, never owned)
+struct Lds3 {
+    int c, ym, yp, ymxm, ypxp, ypxm, ymxp;  // own cell; y-1; y+1; (y-1,x-1); (y+1,x+1); (y+1,x-1); (y-1,x+1)
+};
+__device__ __forceinline__ Lds3 lds3_offsets(int lane, int wy) {
+    const int wm = max(wy - 1, 0) * T3W, wp = min(wy + 1, T3TH - 1) * T3W;
     const int lm = max(lane - 1, 0), lp = min(lane + 1, T3W - 1);
-    const float *p = P + ((((jz - 2) % 3) + 3) % 3) * 2 * T3C;  // plane jz - 2
-    float s[Q3];
+    return Lds3{wy * T3W + lane, wm + lane, wp + lane, wm + lm, wp + lp, wp + lm, wm + lp};
+}
+
+// A level's three steps around its barrier, for input plane jz (in) and
+// centre plane jz - 1.  The level's LDS: M (speeds 17, 18 of plane jz), Z
+// (3..8 of plane jz), P (12, 13 of planes jz, jz - 1, jz - 2, a ring of three
+// slot pairs).  publish3 before the barrier: the thread's own cell of plane
+// jz, P-ring slot pin.
+__device__ __forceinline__ void publish3(float *lds, const float (&in)[Q3], int pin, const Lds3 &d) {
+    float *M = lds, *Z = lds + 2 * T3C, *P = lds + 8 * T3C;
+    M[d.c] = in[17];
+    M[T3C + d.c] = in[18];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) Z[i * T3C + d.c] = in[3 + i];
+    P[(pin * 2) * T3C + d.c] = in[12];
+    P[(pin * 2 + 1) * T3C + d.c] = in[13];
+}
+
+// gather3 after the barrier: the 19 pulls of the centre plane -- which delay
+// line, which LDS slot and which DPP shift feeds which speed.  r0: speeds 0,
+// 1, 2 of the centre plane; zr: its y +- 1 pulls of 3..8 (reload3, one plane
+// ago); r9: speeds 9, 10, 11 of plane jz - 2; pold: the P-ring slot of plane
+// jz - 2.
+__device__ __forceinline__ void gather3(float (&s)[Q3], const float (&in)[Q3], const float (&r0)[3],
+                                        const float (&zr)[6], const float (&r9)[3], const float *lds, int pold,
+                                        const Lds3 &d) {
+    const float *M = lds, *p = lds + 8 * T3C + pold * 2 * T3C;
     s[0] = r0[0];
     s[1] = dpp_from_left(r0[1]);
     s[2] = dpp_from_right(r0[2]);
 #pragma unroll
-    for (int i = 0; i < 6; ++i) s[3 + i] = zr[i];  // plane jz - 1's pulls, read one iteration ago
-    // plane jz's y +- 1 pulls of speeds 3..8, for the next iteration (the slot
-    // is rewritten only after the next barrier of this level's other half)
-    zr[0] = Z[0 * T3C + wm + lane];
-    zr[1] = Z[1 * T3C + wp + lane];
-    zr[2] = Z[2 * T3C + wm + lm];
-    zr[3] = Z[3 * T3C + wp + lp];
-    zr[4] = Z[4 * T3C + wp + lm];
-    zr[5] = Z[5 * T3C + wm + lp];
-    s[9] = r9b[0];
-    s[10] = dpp_from_left(r9b[1]);
-    s[11] = dpp_from_right(r9b[2]);
-    s[12] = p[0 * T3C + wm + lane];
-    s[13] = p[1 * T3C + wp + lane];
+    for (int i = 0; i < 6; ++i) s[3 + i] = zr[i];
+    s[9] = r9[0];
+    s[10] = dpp_from_left(r9[1]);
+    s[11] = dpp_from_right(r9[2]);
+    s[12] = p[d.ym];
+    s[13] = p[T3C + d.yp];
     s[14] = in[14];
     s[15] = dpp_from_right(in[15]);
     s[16] = dpp_from_left(in[16]);
-    s[17] = M[wp + lane];
-    s[18] = M[T3C + wm + lane];
-    float u = 0.f;
-    if (live) {
-        if constexpr (TOL)
-            u = cell3dt(s, out, ob, a.omo, a.k0, a.k1, a.k2, a.w1, a.w2);
-        else
-            u = cell3d(s, out, ob, a.omega, a.omo, a.w1, a.w2);
-    } else {
-#pragma unroll
-        for (int k = 0; k < Q3; ++k) out[k] = 0.f;
-    }
+    s[17] = M[d.yp];
+    s[18] = M[T3C + d.ym];
+}
+
+// reload3 after the barrier: plane jz's y +- 1 pulls of speeds 3..8, for the
+// next plane (the Z slots are rewritten only after this level's next barrier)
+__device__ __forceinline__ void reload3(float (&zr)[6], const float *lds, const Lds3 &d) {
+    const float *Z = lds + 2 * T3C;
+    zr[0] = Z[0 * T3C + d.ym];
+    zr[1] = Z[1 * T3C + d.yp];
+    zr[2] = Z[2 * T3C + d.ymxm];
+    zr[3] = Z[3 * T3C + d.ypxp];
+    zr[4] = Z[4 * T3C + d.ypxm];
+    zr[5] = Z[5 * T3C + d.ymxp];
+}
+
+// the collision of a level: the numerics the pass is instantiated for
+template <bool TOL>
+__device__ __forceinline__ float collide3(const float (&s)[Q3], float (&out)[Q3], bool ob, const Two3Args &a) {
+    if constexpr (TOL)
+        return cell3dt(s, out, ob, a.omo, a.k0, a.k1, a.k2, a.w1, a.w2);
+    else
+        return cell3d(s, out, ob, a.omega, a.omo, a.w1, a.w2);
+}
+
+// One level of the two-step pass for centre plane jz - 1, input plane jz (in).
+// Must be reached by every thread of the block (it holds a barrier).  One
+// register set per delay line, rotated by copies: r0 and zr as gather3's;
+// r9a / r9b: speeds 9, 10, 11 of planes jz - 1 and jz - 2.
+template <bool TOL>
+__device__ __forceinline__ float level3(const float (&in)[Q3], float (&out)[Q3], float *lds, int jz, float (&r0)[3],
+                                        float (&r9a)[3], float (&r9b)[3], float (&zr)[6], const Lds3 &d, bool ob,
+                                        const Two3Args &a) {
+    publish3(lds, in, ((jz % 3) + 3) % 3, d);
+    __syncthreads();
+    float s[Q3];
+    gather3(s, in, r0, zr, r9b, lds, (((jz - 2) % 3) + 3) % 3, d);
+    reload3(zr, lds, d);
+    const float u = collide3<TOL>(s, out, ob, a);
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         r9b[i] = r9a[i];
@@ -502,107 +500,74 @@ __device__ __forceinline__ float level3(const float (&in)[Q3], float (&out)[Q3],
     return u;
 }
 
-// PD: input planes in flight -- 1: plane j+1 while j is computed; 2: also j+2
-// (19 more VGPRs; one 768..960-thread block per CU keeps few loads in flight);
-// 0: plane j+1 is loaded into the input registers once level 1 has consumed
-// them, in flight across level 2 only (19 VGPRs fewer: blocks of 16 rows fit
-// 128 VGPRs).
-template <int TH, bool SKIP, int PD, bool TOL = false>
-__global__ __launch_bounds__(T3W * TH) void step3d_two(Two3Args a) {
-    __shared__ float lds1[T3<TH>::LDS], lds2[T3<TH>::LDS];
-    __shared__ float red[2][TH];
+// PD: input planes in flight -- 1: plane j+1 is loaded while j is computed
+// (its loads stay in flight across both barriers of the iteration); 0 (the
+// default): plane j+1 is loaded into the input registers once level 1 has
+// consumed them, in flight across level 2 only (19 VGPRs fewer).
+template <int PD, bool TOL = false>
+__global__ __launch_bounds__(T3W * T3TH) void step3d_two(Two3Args a) {
+    static_assert(PD == 0 || PD == 1, "two_variant() admits these only");
+    __shared__ float lds1[T3LDS], lds2[T3LDS];
+    __shared__ float red[2][T3TH];
     const int lane = threadIdx.x, wy = __builtin_amdgcn_readfirstlane(threadIdx.y);
     const Blk3 B = blk3_remap();
-    const int ox = B.x * T3OX, oy = B.y * T3<TH>::OY;
-    const bool live1 = !SKIP || (wy >= 1 && wy < TH - 1), live2 = !SKIP || (wy >= 2 && wy < TH - 2);
+    const int ox = B.x * T3OX, oy = B.y * T3OY;
     const int x = (((ox - 2 + lane) % a.nx) + a.nx) % a.nx;
     const int y = (((oy - 2 + wy) % a.ny) + a.ny) % a.ny;
-    const bool own = lane >= 2 && lane < T3W - 2 && wy >= 2 && wy < TH - 2 && ox + lane - 2 < a.nx &&
+    const bool own = lane >= 2 && lane < T3W - 2 && wy >= 2 && wy < T3TH - 2 && ox + lane - 2 < a.nx &&
                      oy + wy - 2 < a.ny;
     const int zs = a.z0 + B.z * a.seg, ze = min(zs + a.seg, a.zn);
     const long long row = (long long)y * a.px + x;
+    const Lds3 d = lds3_offsets(lane, wy);
     float r0a[3] = {0.f, 0.f, 0.f}, r9aa[3] = {0.f, 0.f, 0.f}, r9ba[3] = {0.f, 0.f, 0.f};
     float r0b[3] = {0.f, 0.f, 0.f}, r9ab[3] = {0.f, 0.f, 0.f}, r9bb[3] = {0.f, 0.f, 0.f};
     float zra[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, zrb[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float u1 = 0.f, u2 = 0.f;
+    float u[2] = {0.f, 0.f};
     auto obz = [&](int zz) {  // planes zs-4 .. ze are asked for; only zs-1 .. ze are used
         zz = min(max(zz, -2), a.nz + 1);
         return a.obst[((long long)zz * a.ny + y) * a.nx + x] != 0;
     };
-    // input planes are prefetched PD iterations ahead (their loads stay in
-    // flight across the two barriers of the current iteration)
-    float in[Q3], far[Q3];
+    float in[Q3];
     bool ob1 = obz(zs - 3), ob2 = obz(zs - 4);
     {
         const float *pl = a.fin + (long long)(zs - 2) * a.PL + row;
 #pragma unroll
         for (int k = 0; k < Q3; ++k) in[k] = pl[k * a.KS];
-        if (PD == 2) {
-            const float *pf = a.fin + (long long)min(zs - 1, ze + 1) * a.PL + row;
-#pragma unroll
-            for (int k = 0; k < Q3; ++k) far[k] = pf[k * a.KS];
-        }
     }
     for (int j = zs - 2; j <= ze + 1; ++j) {
         float nin[Q3];
-        const float *pn = a.fin + (long long)min(j + (PD == 0 ? 1 : PD), ze + 1) * a.PL + row;
-        if (PD == 0) {
-        } else if (PD == 2) {
-#pragma unroll
-            for (int k = 0; k < Q3; ++k) nin[k] = far[k];
-#pragma unroll
-            for (int k = 0; k < Q3; ++k) far[k] = pn[k * a.KS];
-        } else {
+        const float *pn = a.fin + (long long)min(j + 1, ze + 1) * a.PL + row;
+        if (PD == 1) {
 #pragma unroll
             for (int k = 0; k < Q3; ++k) nin[k] = pn[k * a.KS];
         }
         ob2 = ob1;
         ob1 = obz(j - 1);
         float o1[Q3], o2[Q3];
-        const float v1 = level3<TH, TOL>(in, o1, lds1, j, r0a, r9aa, r9ba, zra, lane, wy, ob1, live1, a);
-        if (own && j - 1 >= zs && j - 1 < ze) u1 += v1;
+        const float v1 = level3<TOL>(in, o1, lds1, j, r0a, r9aa, r9ba, zra, d, ob1, a);
+        if (own && j - 1 >= zs && j - 1 < ze) u[0] += v1;
         if (PD == 0) {  // level 1 is done with plane j: its registers take plane j + 1
 #pragma unroll
             for (int k = 0; k < Q3; ++k) in[k] = pn[k * a.KS];
         }
-        const float v2 = level3<TH, TOL>(o1, o2, lds2, j - 1, r0b, r9ab, r9bb, zrb, lane, wy, ob2, live2, a);
+        const float v2 = level3<TOL>(o1, o2, lds2, j - 1, r0b, r9ab, r9bb, zrb, d, ob2, a);
         if (own && j - 2 >= zs && j - 2 < ze) {
-            u2 += v2;
-            float *d = a.fout + (long long)(j - 2) * a.PL + row;
+            u[1] += v2;
+            float *dst = a.fout + (long long)(j - 2) * a.PL + row;
 #pragma unroll
-            for (int k = 0; k < Q3; ++k) __builtin_nontemporal_store(o2[k], d + k * a.KS);
+            for (int k = 0; k < Q3; ++k) __builtin_nontemporal_store(o2[k], dst + k * a.KS);
         }
-        if (PD != 0) {
+        if (PD == 1) {
 #pragma unroll
             for (int k = 0; k < Q3; ++k) in[k] = nin[k];
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        u1 += __shfl_down(u1, off, 64);
-        u2 += __shfl_down(u2, off, 64);
-    }
-    if (lane == 0) {
-        red[0][wy] = u1;
-        red[1][wy] = u2;
-    }
-    __syncthreads();
-    if (lane == 0 && wy == 0) {
-        float b1 = red[0][0], b2 = red[1][0];
-#pragma unroll
-        for (int i = 1; i < TH; ++i) {
-            b1 += red[0][i];
-            b2 += red[1][i];
-        }
-        const int blk = a.blk0 + (B.z * gridDim.y + B.y) * gridDim.x + B.x;
-        a.partials[blk] = b1;
-        a.partials[a.nblocks + blk] = b2;
-    }
+    fold_levels(u, red, lane, wy, a.partials, a.nblocks, a.blk0 + (B.z * gridDim.y + B.y) * gridDim.x + B.x);
 }
 
 // ---------------------------------------------------------------------------
 // step3d_three: three time steps per pass (single slab).  The same 64 x 12
-// block and level3 building block with a third level: level 1 computes plane
+// block and level pieces with a third level: level 1 computes plane
 // j-1 at t+1, level 2 plane j-2 at t+2, level 3 plane j-3 at t+3 as input
 // plane j arrives.  A three-cell ring in x and y is recomputed: owned 58 x 6
 // of 64 x 12 loaded cells, three levels of 14 plane slots = 126 KB of LDS (one
@@ -612,9 +577,6 @@ __global__ __launch_bounds__(T3W * TH) void step3d_two(Two3Args a) {
 // lattice carries three ghost planes each side (GZ3), refreshed from the
 // periodic images before every pass.  Same cell3d / cell3dt arithmetic as the
 // other passes: bitwise equal to them (and the oracle) in bitwise mode.
-constexpr int T3OX3 = T3W - 6;  // owned columns
-constexpr int T3TH3 = 12;       // rows (waves) per block
-constexpr int T3OY3 = T3TH3 - 6;
 
 // Per-level delay lines of the three-step pass in two register sets used on
 // alternate planes (the plane loop runs two planes per iteration, set P = 0
@@ -625,11 +587,6 @@ constexpr int T3OY3 = T3TH3 - 6;
 // ~45 moves per plane iteration plus ~40 loop-carried copies at the back edge.)
 struct Lv3 {
     float r0[2][3], r9[2][3], zr[2][6];
-};
-
-// per-thread LDS offsets (floats) of a level's slots, loop-invariant
-struct Lds3 {
-    int c, ym, yp, ymxm, ypxp, ypxm, ymxp;  // own cell; y-1; y+1; (y-1,x-1); (y+1,x+1); (y+1,x-1); (y-1,x+1)
 };
 
 // level3 for the three-step pass: level L (centre plane jz - 1, input plane
@@ -644,50 +601,15 @@ struct Lds3 {
 template <int P, int L, int D, bool TOL>
 __device__ __forceinline__ float level3p(const float (&in)[Q3], float (&out)[Q3], float *lds, int pin, int pold,
                                          Lv3 &st, const Lds3 &d, bool ob, const Two3Args &a) {
-    constexpr int C = T3<T3TH3>::C;
-    float *M = lds, *Z = lds + 2 * C, *Pr = lds + 8 * C;
-    if constexpr (L <= D + 1) {
-        M[d.c] = in[17];
-        M[C + d.c] = in[18];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) Z[i * C + d.c] = in[3 + i];
-        Pr[(pin * 2) * C + d.c] = in[12];
-        Pr[(pin * 2 + 1) * C + d.c] = in[13];
-    }
+    if constexpr (L <= D + 1) publish3(lds, in, pin, d);
     __syncthreads();
     if constexpr (L > D) {
         return 0.f;
     } else {
-        const float *pp = Pr + pold * 2 * C;  // plane jz - 2
         float s[Q3];
-        s[0] = st.r0[P ^ 1][0];
-        s[1] = dpp_from_left(st.r0[P ^ 1][1]);
-        s[2] = dpp_from_right(st.r0[P ^ 1][2]);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) s[3 + i] = st.zr[P ^ 1][i];
-        // plane jz's y +- 1 pulls of speeds 3..8, for the next plane (each
-        // slot is rewritten only after the next barrier of this level)
-        st.zr[P][0] = Z[0 * C + d.ym];
-        st.zr[P][1] = Z[1 * C + d.yp];
-        st.zr[P][2] = Z[2 * C + d.ymxm];
-        st.zr[P][3] = Z[3 * C + d.ypxp];
-        st.zr[P][4] = Z[4 * C + d.ypxm];
-        st.zr[P][5] = Z[5 * C + d.ymxp];
-        s[9] = st.r9[P][0];
-        s[10] = dpp_from_left(st.r9[P][1]);
-        s[11] = dpp_from_right(st.r9[P][2]);
-        s[12] = pp[d.ym];
-        s[13] = pp[C + d.yp];
-        s[14] = in[14];
-        s[15] = dpp_from_right(in[15]);
-        s[16] = dpp_from_left(in[16]);
-        s[17] = M[d.yp];
-        s[18] = M[C + d.ym];
-        float u;
-        if constexpr (TOL)
-            u = cell3dt(s, out, ob, a.omo, a.k0, a.k1, a.k2, a.w1, a.w2);
-        else
-            u = cell3d(s, out, ob, a.omega, a.omo, a.w1, a.w2);
+        gather3(s, in, st.r0[P ^ 1], st.zr[P ^ 1], st.r9[P], lds, pold, d);
+        reload3(st.zr[P], lds, d);
+        const float u = collide3<TOL>(s, out, ob, a);
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             st.r9[P][i] = in[9 + i];
@@ -705,8 +627,7 @@ __device__ __forceinline__ float level3p(const float (&in)[Q3], float (&out)[Q3]
 // engine keeps Q3 x KS x 4 B below 2^31 for this pass).
 template <int D, bool TOL>
 __device__ __forceinline__ void three_rows(const Two3Args &a, const Lds3 &d, float *lds1, float *lds2, float *lds3,
-                                           int x, int y, unsigned rowb, bool own, int zs, int ze, float &u1,
-                                           float &u2, float &u3) {
+                                           int x, int y, unsigned rowb, bool own, int zs, int ze, float (&u)[3]) {
     Lv3 s1{}, s2{}, s3{};
     const unsigned nrec = (unsigned)(Q3 * a.KS * 4);
     const int ks4 = (int)(a.KS * 4);
@@ -738,14 +659,14 @@ __device__ __forceinline__ void three_rows(const Two3Args &a, const Lds3 &d, flo
         }
         float o1[Q3], o2[Q3], o3[Q3];
         const float v1 = level3p<P, 1, D, TOL>(in, o1, lds1, sj, sm2, s1, d, ob1, a);
-        if (D == 3 && own && j - 1 >= zs && j - 1 < ze) u1 += v1;
+        if (D == 3 && own && j - 1 >= zs && j - 1 < ze) u[0] += v1;
         load(min(j + 1, ze + 2));
         const float v2 = level3p<P, 2, D, TOL>(o1, o2, lds2, sm1, sj, s2, d, ob2, a);
-        if (D == 3 && own && j - 2 >= zs && j - 2 < ze) u2 += v2;
+        if (D == 3 && own && j - 2 >= zs && j - 2 < ze) u[1] += v2;
         const float v3 = level3p<P, 3, D, TOL>(o2, o3, lds3, sm2, sm1, s3, d, ob3, a);
         if constexpr (D == 3) {
             if (own && j - 3 >= zs && j - 3 < ze) {
-                u3 += v3;
+                u[2] += v3;
                 const auto r = rsrc(a.fout + (long long)(j - 3) * a.PL);
 #pragma unroll
                 // plain (temporal) stores: x-neighbouring blocks run on one XCD
@@ -767,66 +688,31 @@ __device__ __forceinline__ void three_rows(const Two3Args &a, const Lds3 &d, flo
 }
 
 // SKIP: rows no later level reads skip the collision (level 1: rows 1..10,
-// level 2: 2..9, level 3: 3..8 live), as step3d_two's SKIP -- each wave runs
-// the plane loop instantiated for its row's live depth.
+// level 2: 2..9, level 3: 3..8 live) -- each wave runs the plane loop
+// instantiated for its row's live depth.
 template <bool TOL, bool SKIP>
-__global__ __launch_bounds__(T3W *T3TH3) void step3d_three(Two3Args a) {
-    __shared__ float lds1[T3<T3TH3>::LDS], lds2[T3<T3TH3>::LDS], lds3[T3<T3TH3>::LDS];
-    __shared__ float red[3][T3TH3];
+__global__ __launch_bounds__(T3W *T3TH) void step3d_three(Two3Args a) {
+    __shared__ float lds1[T3LDS], lds2[T3LDS], lds3[T3LDS];
+    __shared__ float red[3][T3TH];
     const int lane = threadIdx.x, wy = __builtin_amdgcn_readfirstlane(threadIdx.y);
     const Blk3 B = blk3_remap();
     const int ox = B.x * T3OX3, oy = B.y * T3OY3;
     const int x = (((ox - 3 + lane) % a.nx) + a.nx) % a.nx;
     const int y = (((oy - 3 + wy) % a.ny) + a.ny) % a.ny;
-    const bool own = lane >= 3 && lane < T3W - 3 && wy >= 3 && wy < T3TH3 - 3 && ox + lane - 3 < a.nx &&
+    const bool own = lane >= 3 && lane < T3W - 3 && wy >= 3 && wy < T3TH - 3 && ox + lane - 3 < a.nx &&
                      oy + wy - 3 < a.ny;
     const int zs = a.z0 + B.z * a.seg, ze = min(zs + a.seg, a.zn);
     const unsigned rowb = (unsigned)(y * a.px + x) * 4u;  // byte offset of the lane's cell in a speed plane
-    Lds3 d;
-    {
-        const int wm = max(wy - 1, 0) * T3W, wp = min(wy + 1, T3TH3 - 1) * T3W;
-        const int lm = max(lane - 1, 0), lp = min(lane + 1, T3W - 1);
-        d.c = wy * T3W + lane;
-        d.ym = wm + lane;
-        d.yp = wp + lane;
-        d.ymxm = wm + lm;
-        d.ypxp = wp + lp;
-        d.ypxm = wp + lm;
-        d.ymxp = wm + lp;
-    }
-    float u1 = 0.f, u2 = 0.f, u3 = 0.f;
-    const int depth = SKIP ? min(min(wy, T3TH3 - 1 - wy), 3) : 3;  // wave-uniform
+    const Lds3 d = lds3_offsets(lane, wy);
+    float u[3] = {0.f, 0.f, 0.f};
+    const int depth = SKIP ? min(min(wy, T3TH - 1 - wy), 3) : 3;  // wave-uniform
     switch (depth) {
-        case 0: three_rows<0, TOL>(a, d, lds1, lds2, lds3, x, y, rowb, own, zs, ze, u1, u2, u3); break;
-        case 1: three_rows<1, TOL>(a, d, lds1, lds2, lds3, x, y, rowb, own, zs, ze, u1, u2, u3); break;
-        case 2: three_rows<2, TOL>(a, d, lds1, lds2, lds3, x, y, rowb, own, zs, ze, u1, u2, u3); break;
-        default: three_rows<3, TOL>(a, d, lds1, lds2, lds3, x, y, rowb, own, zs, ze, u1, u2, u3); break;
+        case 0: three_rows<0, TOL>(a, d, lds1, lds2, lds3, x, y, rowb, own, zs, ze, u); break;
+        case 1: three_rows<1, TOL>(a, d, lds1, lds2, lds3, x, y, rowb, own, zs, ze, u); break;
+        case 2: three_rows<2, TOL>(a, d, lds1, lds2, lds3, x, y, rowb, own, zs, ze, u); break;
+        default: three_rows<3, TOL>(a, d, lds1, lds2, lds3, x, y, rowb, own, zs, ze, u); break;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        u1 += __shfl_down(u1, off, 64);
-        u2 += __shfl_down(u2, off, 64);
-        u3 += __shfl_down(u3, off, 64);
-    }
-    if (lane == 0) {
-        red[0][wy] = u1;
-        red[1][wy] = u2;
-        red[2][wy] = u3;
-    }
-    __syncthreads();
-    if (lane == 0 && wy == 0) {
-        float b1 = red[0][0], b2 = red[1][0], b3 = red[2][0];
-#pragma unroll
-        for (int i = 1; i < T3TH3; ++i) {
-            b1 += red[0][i];
-            b2 += red[1][i];
-            b3 += red[2][i];
-        }
-        const int blk = a.blk0 + (B.z * gridDim.y + B.y) * gridDim.x + B.x;
-        a.partials[blk] = b1;
-        a.partials[a.nblocks + blk] = b2;
-        a.partials[2 * a.nblocks + blk] = b3;
-    }
+    fold_levels(u, red, lane, wy, a.partials, a.nblocks, a.blk0 + (B.z * gridDim.y + B.y) * gridDim.x + B.x);
 }
 
 __global__ __launch_bounds__(BLOCK) void reduce3d(const float *partials, int n, float *av_local, int t) {
@@ -847,16 +733,21 @@ __global__ __launch_bounds__(BLOCK) void init3d(float *base, long long planes, l
     for (int k = 1; k < Q3; ++k) d[k * KS] = (k <= 4 || k == 9 || k == 14) ? c1 : c2;
 }
 
-// AoS [nzs][ny][nx][19] staging <-> lattice interior
-__global__ __launch_bounds__(BLOCK) void aos_to_soa3d(const float *aos, float *f, long long PL, long long KS, int px,
-                                                     int nx, int ny, long long n) {
-    const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
+// AoS [nzs][ny][nx][19] staging <-> lattice interior: where cell i of the
+// staging array lies in the lattice (speed 0; floats from its origin)
+__device__ __forceinline__ long long cell_offset3(long long i, long long PL, int px, int nx, int ny) {
     const long long zy = i / nx;
     const int x = (int)(i - zy * nx);
     const int y = (int)(zy % ny);
     const long long z = zy / ny;
-    float *d = f + z * PL + (long long)y * px + x;
+    return z * PL + (long long)y * px + x;
+}
+
+__global__ __launch_bounds__(BLOCK) void aos_to_soa3d(const float *aos, float *f, long long PL, long long KS, int px,
+                                                     int nx, int ny, long long n) {
+    const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    float *d = f + cell_offset3(i, PL, px, nx, ny);
 #pragma unroll
     for (int k = 0; k < Q3; ++k) d[k * KS] = aos[i * Q3 + k];
 }
@@ -865,25 +756,20 @@ __global__ __launch_bounds__(BLOCK) void soa_to_aos3d(const float *f, float *aos
                                                      int nx, int ny, long long n) {
     const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
-    const long long zy = i / nx;
-    const int x = (int)(i - zy * nx);
-    const int y = (int)(zy % ny);
-    const long long z = zy / ny;
-    const float *s = f + z * PL + (long long)y * px + x;
+    const float *s = f + cell_offset3(i, PL, px, nx, ny);
 #pragma unroll
     for (int k = 0; k < Q3; ++k) aos[i * Q3 + k] = s[k * KS];
 }
 
 // ---- launch wrappers (lbm3d_engine.hpp) ----
 
-// 12 rows without skip, late load (default) or one plane prefetched.  Blocks
-// of 14-16 rows, the row skip and two prefetched planes were measured and
-// removed (profiles/r02/d3q19/ab_two_th_skip_pd.log, profiles/r03/d3q19/ab_pd.log).
-int two_variant(int th, bool skip, int pd) { return (th == 12 && !skip && (pd == 0 || pd == 1)) ? pd : -1; }
+// 12 rows without skip, late load (default) or one plane prefetched: the
+// instantiations of step3d_two<PD> (see the block constants above)
+int two_variant(int th, bool skip, int pd) { return (th == T3TH && !skip && (pd == 0 || pd == 1)) ? pd : -1; }
 
-// grid of an n-step pass: owned tiles of T3OX x 8 (n = 2, 12-row blocks) or T3OX3 x T3OY3 (n = 3)
+// grid of an n-step pass: owned tiles of T3OX x T3OY (n = 2) or T3OX3 x T3OY3 (n = 3)
 static dim3 pass3d_grid(int n, int nx, int ny, int planes, int seg) {
-    const int ox = n == 3 ? T3OX3 : T3OX, oy = n == 3 ? T3OY3 : T3<12>::OY;
+    const int ox = n == 3 ? T3OX3 : T3OX, oy = n == 3 ? T3OY3 : T3OY;
     return dim3((nx + ox - 1) / ox, (ny + oy - 1) / oy, (planes + seg - 1) / seg);
 }
 
@@ -894,13 +780,13 @@ int pass3d_blocks(int n, int nx, int ny, int planes, int seg) {
 
 hipError_t launch_step3d_two(const Two3Args &a, int variant, bool tol, hipStream_t s) {
     if (a.zn <= a.z0) return hipSuccess;
-    const dim3 g = pass3d_grid(2, a.nx, a.ny, a.zn - a.z0, a.seg), b(T3W, 12);
-    if (tol)  // the default block only (12 rows, no skip, late load)
-        hipLaunchKernelGGL((step3d_two<12, false, 0, true>), g, b, 0, s, a);
+    const dim3 g = pass3d_grid(2, a.nx, a.ny, a.zn - a.z0, a.seg), b(T3W, T3TH);
+    if (tol)  // the default load schedule only (late load)
+        hipLaunchKernelGGL((step3d_two<0, true>), g, b, 0, s, a);
     else if (variant == 0)
-        hipLaunchKernelGGL((step3d_two<12, false, 0>), g, b, 0, s, a);
+        hipLaunchKernelGGL((step3d_two<0>), g, b, 0, s, a);
     else if (variant == 1)
-        hipLaunchKernelGGL((step3d_two<12, false, 1>), g, b, 0, s, a);
+        hipLaunchKernelGGL((step3d_two<1>), g, b, 0, s, a);
     else
         return hipErrorInvalidValue;  // no such instantiation (create rejects it)
     return hipGetLastError();
@@ -908,15 +794,10 @@ hipError_t launch_step3d_two(const Two3Args &a, int variant, bool tol, hipStream
 
 hipError_t launch_step3d_three(const Two3Args &a, bool tol, bool skip, hipStream_t s) {
     if (a.zn <= a.z0) return hipSuccess;
-    const dim3 g = pass3d_grid(3, a.nx, a.ny, a.zn - a.z0, a.seg), b(T3W, T3TH3);
-    if (tol && skip)
-        hipLaunchKernelGGL((step3d_three<true, true>), g, b, 0, s, a);
-    else if (tol)
-        hipLaunchKernelGGL((step3d_three<true, false>), g, b, 0, s, a);
-    else if (skip)
-        hipLaunchKernelGGL((step3d_three<false, true>), g, b, 0, s, a);
-    else
-        hipLaunchKernelGGL((step3d_three<false, false>), g, b, 0, s, a);
+    const dim3 g = pass3d_grid(3, a.nx, a.ny, a.zn - a.z0, a.seg), b(T3W, T3TH);
+    void (*const kernel[2][2])(Two3Args) = {{step3d_three<false, false>, step3d_three<false, true>},
+                                            {step3d_three<true, false>, step3d_three<true, true>}};
+    hipLaunchKernelGGL(kernel[tol][skip], g, b, 0, s, a);
     return hipGetLastError();
 }
 

@@ -79,10 +79,10 @@ struct Two3Args {
 // One step of `planes` planes from a.z0: step3d, or (pair) step3d_pair<zb, nt>.
 int step3d_blocks(int nx, int ny, int planes, bool pair, int zb);
 hipError_t launch_step3d(const Step3Args &a, int planes, bool pair, int zb, bool nt, hipStream_t s);
-// switch key of the instantiated step3d_two<TH, SKIP, PD> variants, -1 if none
+// switch key of the instantiated step3d_two<PD> variants (12 rows, no skip, PD 0 | 1), -1 if none
 int two_variant(int th, bool skip, int pd);
 // n steps (n = 2, 3) of planes [a.z0, a.zn) in segments of a.seg planes:
-// step3d_two<12, false, variant> or (tol) its tolerance form; step3d_three<tol, skip>.
+// step3d_two<variant> or (tol) its tolerance form; step3d_three<tol, skip>.
 int pass3d_blocks(int n, int nx, int ny, int planes, int seg);
 hipError_t launch_step3d_two(const Two3Args &a, int variant, bool tol, hipStream_t s);
 hipError_t launch_step3d_three(const Two3Args &a, bool tol, bool skip, hipStream_t s);

@@ -135,6 +135,37 @@ def test_d3q19_bitwise_single_slab(gpu_lib, nx, ny, nz, pair, two, seg, monkeypa
     np.testing.assert_allclose(av, ref_av, rtol=1e-5)
 
 
+_PAIR_CASE = {}
+
+
+def _pair_case():
+    """130 x 9 x 11, 3 steps: problem and oracle result, computed once for the cases below."""
+    if not _PAIR_CASE:
+        p, obst, c0 = _problem(130, 9, 11, 150)
+        _PAIR_CASE["v"] = (p, obst, c0) + oracle.run3d(p, obst, 3, c0)
+    return _PAIR_CASE["v"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nt", ["0", "1"])
+@pytest.mark.parametrize("zb,parts", [("1", 1), ("2", 1), ("4", 1), ("8", 1), ("8", 2)])
+def test_d3q19_pair_kernel_variants_bitwise(gpu_lib, zb, parts, nt, monkeypatch):
+    """Every step3d_pair<ZB, NT> instantiation (LBM3D_ZB 1, 2, 4, 8 planes per
+    block; LBM3D_NT plain or non-temporal stores), three pair launches each:
+    130 x 9 x 11 gives two pair blocks in x (the second with one active lane),
+    three row blocks (the last with one row) and 11 planes, which no ZB divides;
+    in 2 z slabs (ZB = 8) the boundary and interior launches each have fewer
+    planes than one block walks."""
+    monkeypatch.setenv("LBM3D_ZB", zb)
+    monkeypatch.setenv("LBM3D_NT", nt)
+    monkeypatch.setenv("LBM3D_TWO", "0")
+    p, obst, c0, ref, ref_av = _pair_case()
+    cells, av = _gpu3d(gpu_lib, p, obst, c0, 3, parts=parts, devices=[0], numerics="bitwise",
+                       expect=_forms(3, p.nx, two=False))
+    assert np.array_equal(cells, ref)
+    np.testing.assert_allclose(av, ref_av, rtol=1e-5)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("parts", [2, 3, 4, 7])
 def test_d3q19_slabs_loopback_bitwise(gpu_lib, parts):
