@@ -693,6 +693,7 @@ void lbm3d_handle::destroy() {
     walls_release();
     avg_end();
     tracer_end();
+    scalar_end();
     grad_release();
     stress_release();
     for (auto &s : slabs) {

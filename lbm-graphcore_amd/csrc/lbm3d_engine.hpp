@@ -11,6 +11,8 @@
 //   lbm3d_stress.hip   strain rate and wall shear from the non-equilibrium moments (kernel + host side);
 //   lbm3d_binned.hip   sums over box-shaped bins of the current lattice (kernel + host side);
 //   lbm3d_tracers.hip  Lagrangian tracers and point probes (host side; kernels in lbm_tracers.hpp);
+//   lbm3d_scalar.hip   passive scalar: a D3Q7 lattice beside the flow lattice (step kernel, host side;
+//                      shared parts in lbm_scalar.hpp);
 //   lbm3d_abi.hip      the extern "C" functions and the RCCL posting order.
 // The diagnostics units (fields to binned) share their host paths through
 // lbm_diag_host.hpp and their cell reads and block fold through lbm_quad.hpp.
@@ -37,6 +39,9 @@ struct State;  // accumulators of a handle that is averaging (lbm_moments.hpp)
 }
 namespace tracer {
 struct State;  // point set of a handle that keeps tracers (lbm_tracers.hpp)
+}
+namespace scalar {
+struct State;  // scalar lattice of a handle that carries a passive scalar (lbm_scalar.hpp)
 }
 namespace grad {
 struct Grad3Args;  // lbm_gradients.hpp
@@ -282,4 +287,13 @@ struct lbm3d_handle {
     void tracer_sample(double *const (&host)[4]);
     void tracer_store(double *const (&host)[3], uint8_t *blocked);
     void tracer_end();
+    // lbm3d_scalar.hip (include/lbm_scalar_hip.h)
+    lbm::scalar::State *scalars = nullptr;  // set between scalar_begin and scalar_end
+    void scalar_begin(float omega_s, const float *phi0);
+    void scalar_set_fixed(int64_t n, const int32_t *x, const int32_t *y, const int32_t *z, const float *value);
+    void scalar_advance(int steps);
+    int64_t scalar_steps();
+    void scalar_store(float *phi, float *g);
+    void scalar_stats(double *total, float *min, float *max);
+    void scalar_end();
 };

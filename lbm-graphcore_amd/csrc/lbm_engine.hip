@@ -929,6 +929,7 @@ void lbm_handle::destroy() {
     forces_release();
     avg_end();
     tracer_end();
+    scalar_end();
     grad_release();
     stress_release();
     for (auto &s : subs) {

@@ -17,6 +17,9 @@
 //   lbm_tracers.hip       Lagrangian tracers and point probes: a point set
 //                         on the device, interpolated from the current
 //                         lattice (host side; kernels in lbm_tracers.hpp);
+//   lbm_scalar.hip        passive scalar: a D2Q5 lattice beside the flow
+//                         lattice, advanced over the frozen flow (step kernel,
+//                         host side; shared parts in lbm_scalar.hpp);
 //   lbm_exchange.hip      partition rule, torus neighbours, halo destinations,
 //                         the posted exchange (RCCL or device copies);
 //   lbm_split.hip         work decomposition: boundary / interior split,
@@ -115,6 +118,9 @@ struct GradArgs;  // lbm_gradients.hpp
 }
 namespace tracer {
 struct State;  // point set of a handle that keeps tracers (lbm_tracers.hpp)
+}
+namespace scalar {
+struct State;  // scalar lattice of a handle that carries a passive scalar (lbm_scalar.hpp)
 }
 namespace stress {
 struct State;       // near-wall class maps of a handle that asked for strain statistics (lbm_stress.hip)
@@ -465,5 +471,14 @@ struct lbm_handle {
     void tracer_sample(double *ux, double *uy, double *pressure);
     void tracer_store(double *x, double *y, uint8_t *blocked);
     void tracer_end();
+    // passive scalar (lbm_scalar.hip; include/lbm_scalar_hip.h)
+    lbm::scalar::State *scalars = nullptr;  // set between scalar_begin and scalar_end
+    void scalar_begin(float omega_s, const float *phi0);
+    void scalar_set_fixed(int64_t n, const int32_t *x, const int32_t *y, const float *value);
+    void scalar_advance(int steps);
+    int64_t scalar_steps();
+    void scalar_store(float *phi, float *g);
+    void scalar_stats(double *total, float *min, float *max);
+    void scalar_end();
     void destroy();
 };

@@ -4,7 +4,8 @@
 //   lbm_runner --params P --obstacles O [-n N] [--device gpu|loopback|cpu] [-d] [--exe ignored]
 //              [--runs 5] [--kernel auto|resident|stream|step2|vec4|scalar|pipeline] [--spl S] [--out-dir DIR]
 //              [--tolerance] [--device-fields] [--forces] [--mean-every N] [--gradients] [--stress] [--binned BWxBH]
-//              [--tracers FILE [--trace-every N] [--trace-scheme euler|heun]] [--json FILE]
+//              [--tracers FILE [--trace-every N] [--trace-scheme euler|heun]]
+//              [--scalar FILE [--scalar-omega W] [--scalar-stride N]] [--json FILE]
 //
 // Flow (same program numbering as the reference):
 //   load params/obstacles -> initialise cells on host -> create engine
@@ -51,11 +52,18 @@
 // -- through lbm_tracer_begin / _advance / _store on the GPU, through
 // lbmhost::tracerAdvance (lbm_tracer_advance_ref over the stored cells'
 // velocities) with --device cpu.
+// --scalar FILE reads one cell per line, `x y value [1]` (a trailing 1 makes the
+// cell a fixed one: a dye inlet, a heated body; unlisted cells hold 0), runs
+// the first run coupled with a passive scalar of relaxation rate
+// --scalar-omega (default 1.0) -- --scalar-stride N (default 1) flow steps,
+// then as many scalar steps over the frozen lattice, repeated -- and writes
+// scalar_state.dat after the run: `x y phi` per cell, x fastest, phi in %.9g
+// (lbm_scalar_hip.h).  GPU only.
 // --device loopback places all N sub-domains on GPU 0 (the emulator analogue
 // of --device ipumodel: exercises the multi-GPU halo path on one device).
 // --device cpu runs the same fused step on the host's cores (lbm_cpu.hpp:
 // OpenMP rows, bitwise equal to the GPU engine's default numerics); the
-// GPU-only options (-n, --tolerance, --kernel, --spl, --graph-steps, --device-fields, --mean-every) do not
+// GPU-only options (-n, --tolerance, --kernel, --spl, --graph-steps, --device-fields, --mean-every, --scalar) do not
 // apply there and are refused with a message.
 #include <algorithm>
 #include <cstdio>
@@ -75,6 +83,7 @@
 #include "lbm_forces_hip.h"
 #include "lbm_gradients_hip.h"
 #include "lbm_host.hpp"
+#include "lbm_scalar_hip.h"
 #include "lbm_stress_hip.h"
 #include "lbm_tracers_hip.h"
 
@@ -114,6 +123,12 @@ void usage(const char *exe) {
               << "                       the points moved with the flow (id x y blocked per point)\n"
               << "      --trace-every arg  steps between two moves of the tracers (default: 10)\n"
               << "      --trace-scheme arg euler or heun (default: heun)\n"
+              << "      --scalar arg     file of `x y value [1]` lines (1 = fixed cell; unlisted cells hold 0): carry a\n"
+              << "                       passive scalar with the first run and also write scalar_state.dat (x y phi)\n"
+              << "      --scalar-omega arg   relaxation rate of the scalar, inside (0, 2) (default: 1.0; the\n"
+              << "                       diffusivity is (1/arg - 1/2) / 3)\n"
+              << "      --scalar-stride arg  flow steps between two updates of the scalar, which then advances as many\n"
+              << "                       steps over the frozen flow (default: 1, the exact coupling)\n"
               << "      --out-dir arg    directory for av_vels.dat / final_state.dat (default: .)\n"
               << "      --graph-steps arg  replay the step loop as hipGraphs of 2*arg launches (0 = library default, <0 = off)\n"
               << "      --dump-partitioning arg  write the sub-domain decomposition as JSON\n"
@@ -225,6 +240,9 @@ int main(int argc, char *argv[]) {
     std::string paramsFile, obstaclesFile, device = "gpu", exeFile, kernel = "auto", outDir = ".", dumpFile, jsonFile;
     std::string tracersFile, traceSchemeName = "heun";
     int traceEvery = 10;
+    std::string scalarFile;
+    float scalarOmega = 1.0f;
+    int scalarStride = 1;
     std::vector<std::string> gpuOnly;  // GPU-only options given on the command line
     int spl = 0;
     int numGpus = 1, runs = 5, graphSteps = 0, meanEvery = 0, binW = 0, binH = 0;
@@ -303,6 +321,18 @@ int main(int argc, char *argv[]) {
                 usage(argv[0]);
                 return EXIT_FAILURE;
             }
+        } else if (a == "--scalar") {
+            if (!next(scalarFile)) { usage(argv[0]); return EXIT_FAILURE; }
+            gpuOnly.push_back(a);
+        } else if (a == "--scalar-omega") {
+            if (!next(v)) { usage(argv[0]); return EXIT_FAILURE; }
+            scalarOmega = std::strtof(v.c_str(), nullptr);
+            gpuOnly.push_back(a);
+        } else if (a == "--scalar-stride") {
+            if (!next(v)) { usage(argv[0]); return EXIT_FAILURE; }
+            scalarStride = std::atoi(v.c_str());
+            if (scalarStride < 1) { usage(argv[0]); return EXIT_FAILURE; }
+            gpuOnly.push_back(a);
         } else if (a == "--out-dir") {
             if (!next(outDir)) { usage(argv[0]); return EXIT_FAILURE; }
         } else if (a == "--graph-steps") {
@@ -353,6 +383,41 @@ int main(int argc, char *argv[]) {
         }
         tracers = lbmhost::readTracers(tracersFile, *params);
         if (!tracers.has_value()) return EXIT_FAILURE;
+    }
+    // --scalar: phi0 of every cell and the fixed list
+    std::vector<float> scalarPhi, scalarFixedValue;
+    std::vector<int32_t> scalarFixedX, scalarFixedY;
+    if (!scalarFile.empty()) {
+        if (meanEvery > 0 || tracers.has_value()) {
+            std::cerr << "--scalar, --tracers and --mean-every each take the run in their own chunks: give one of them"
+                      << std::endl;
+            return EXIT_FAILURE;
+        }
+        std::ifstream f(scalarFile);
+        if (!f) {
+            std::cerr << "Could not read the scalar from " << scalarFile << std::endl;
+            return EXIT_FAILURE;
+        }
+        scalarPhi.assign(params->nx * params->ny, 0.f);
+        std::string line;
+        while (std::getline(f, line)) {
+            if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+            long x = -1, y = -1;
+            float value = 0.f;
+            int fixed = 0;
+            const int got = sscanf(line.c_str(), "%ld %ld %f %d", &x, &y, &value, &fixed);
+            if (got < 3 || x < 0 || y < 0 || (size_t)x >= params->nx || (size_t)y >= params->ny ||
+                (got == 4 && fixed != 0 && fixed != 1)) {
+                std::cerr << "Malformed scalar line (x y value [1] inside the grid expected): " << line << std::endl;
+                return EXIT_FAILURE;
+            }
+            scalarPhi[(size_t)y * params->nx + x] = value;
+            if (fixed == 1) {
+                scalarFixedX.push_back((int32_t)x);
+                scalarFixedY.push_back((int32_t)y);
+                scalarFixedValue.push_back(value);
+            }
+        }
     }
     if (!dumpFile.empty()) {
         // partitioning.json in the layout of grids::serializeToJson
@@ -469,12 +534,26 @@ int main(int argc, char *argv[]) {
                 done += n;
             }
         });
+    } else if (!scalarFile.empty()) {
+        total_compute_time += lbmhost::timedStep("Running LBM", [&]() {
+            lbmhost::check(lbm_scalar_begin(h, scalarOmega, scalarPhi.data()), h, "lbm_scalar_begin");
+            lbmhost::check(lbm_scalar_set_fixed(h, (int64_t)scalarFixedX.size(), scalarFixedX.data(),
+                                                scalarFixedY.data(), scalarFixedValue.data()),
+                           h, "lbm_scalar_set_fixed");
+            for (int done = 0; done < (int)params->maxIters;) {
+                const int n = std::min(scalarStride, (int)params->maxIters - done);
+                lbmhost::check(lbm_run_steps(h, n, done == 0), h, "lbm_run_steps");
+                lbmhost::check(lbm_store(h, nullptr, av_vels.data() + done, n), h, "lbm_store");
+                lbmhost::check(lbm_scalar_advance(h, n), h, "lbm_scalar_advance");
+                done += n;
+            }
+        });
     } else {
         total_compute_time += lbmhost::timedStep("Running LBM", [&]() { lbmhost::check(lbm_run(h), h, "lbm_run"); });
     }
     std::vector<float> means[LBM_AVG_FIELDS];         // --mean-every: mean_state.dat's columns, planar
-    // --mean-every and --tracers gathered av_vels per chunk: the last run's would overwrite them
-    float *const avOut = (meanEvery > 0 || tracers.has_value()) ? nullptr : av_vels.data();
+    // --mean-every, --tracers and --scalar gathered av_vels per chunk: the last run's would overwrite them
+    float *const avOut = (meanEvery > 0 || tracers.has_value() || !scalarFile.empty()) ? nullptr : av_vels.data();
     std::vector<float> f_ux, f_uy, f_u, f_pressure;  // --device-fields: final_state.dat's columns, planar
     lbmhost::BodyForces bodyForces;                   // --forces: forces.dat
     std::vector<float> grads[LBM_GRAD_FIELDS];        // --gradients: gradient_state.dat's columns, planar
@@ -535,6 +614,10 @@ int main(int argc, char *argv[]) {
                            "lbm_tracer_store");
             lbmhost::check(lbm_tracer_end(h), h, "lbm_tracer_end");
         }
+        if (!scalarFile.empty()) {
+            lbmhost::check(lbm_scalar_store(h, scalarPhi.data(), nullptr), h, "lbm_scalar_store");
+            lbmhost::check(lbm_scalar_end(h), h, "lbm_scalar_end");
+        }
         if (forces) {
             std::vector<int32_t> labels;
             const int32_t nbodies = lbmhost::labelBodies(*obstacles, labels);
@@ -558,6 +641,18 @@ int main(int argc, char *argv[]) {
                                       lbmhost::nearWall(*obstacles));
         if (binW > 0) lbmhost::writeBinnedState(outDir + "/binned_state.dat", binned);
         if (tracers.has_value()) lbmhost::writeTracers(outDir + "/tracers.dat", *tracers);
+        if (!scalarFile.empty()) {
+            // scalar_state.dat: `x y phi` per cell, x fastest; %.9g reads back to the same float
+            FILE *out = fopen((outDir + "/scalar_state.dat").c_str(), "w");
+            if (!out) {
+                std::cerr << "Could not write scalar_state.dat" << std::endl;
+            } else {
+                for (size_t y = 0; y < params->ny; ++y)
+                    for (size_t x = 0; x < params->nx; ++x)
+                        fprintf(out, "%zu %zu %.9g\n", x, y, (double)scalarPhi[y * params->nx + x]);
+                fclose(out);
+            }
+        }
         if (!means[0].empty()) lbmhost::writeMeanState(outDir + "/mean_state.dat", *params, *obstacles, means);
         lbmhost::writeAverageVelocities(outDir + "/av_vels.dat", av_vels);
         if (deviceFields)

@@ -22,6 +22,9 @@
 * tracer_interp, tracer_advance, tracer_blocked (+ ...3d), tracer_wrap, read_tracers
                         -- the tracers and point probes of include/lbm_tracers_hip.h in float64
                            numpy (Engine.tracer_sample(), .tracers_advance(), .tracers())
+* scalar_init, scalar_step, scalar_phi, scalar_apply_fixed, scalar_stats (+ ...3d)
+                        -- the passive scalar of include/lbm_scalar_hip.h in fp32 numpy
+                           (Engine.scalar_begin(), .scalar_advance(), .scalar(), .scalar_stats())
 
 Error behaviour follows the reference: loaders return None (std::nullopt)
 and print the reference's message on stderr.  One deliberate strengthening:
@@ -782,6 +785,127 @@ def read_tracers(filename: str):
             y.append(float(t[2]))
             b.append(int(t[3]))
     return np.asarray(x, np.float64), np.asarray(y, np.float64), np.asarray(b, np.uint8)
+
+
+# ---- passive scalar (include/lbm_scalar_hip.h) ----
+#
+# The header's definition in fp32 numpy, one ufunc per operation so that every
+# operation is rounded on its own.  Populations are planar float32[5][ny][nx]
+# (D2Q5) or float32[7][nz][ny][nx] (D3Q7).  The tables below are read at call
+# time: a test plants an error by replacing one.
+
+SCALAR_W = (np.float32(1) / np.float32(3), np.float32(1) / np.float32(6))     # begin / equilibrium weights: rest, moving
+SCALAR_W3D = (np.float32(0.25), np.float32(0.125))
+SCALAR_OPP = (0, 3, 4, 1, 2)
+SCALAR_OPP3D = (0, 2, 1, 4, 3, 6, 5)
+# per moving speed: (velocity component, array axis it moves along, sign)
+SCALAR_SPEEDS = ((0, 1, +1), (1, 0, +1), (0, 1, -1), (1, 0, -1))                          # E N W S
+SCALAR_SPEEDS3D = ((0, 2, +1), (0, 2, -1), (1, 1, +1), (1, 1, -1), (2, 0, +1), (2, 0, -1))   # +x -x +y -y +z -z
+
+
+def scalar_diffusivity(omega_s, dims: int = 2) -> float:
+    """D = (1 / omega_s - 1/2) / 3 (2-D) or / 4 (3-D)."""
+    return (1.0 / float(omega_s) - 0.5) / (3.0 if dims == 2 else 4.0)
+
+
+def _scalar_init(phi0, w, q):
+    phi0 = np.ascontiguousarray(phi0, np.float32)
+    moving = phi0 * w[1]
+    return np.stack([phi0 * w[0]] + [moving] * (q - 1))
+
+
+def scalar_init(phi0) -> np.ndarray:
+    """float32[5][ny][nx]: the begin state of phi0 (lbm_scalar_begin)."""
+    return _scalar_init(phi0, SCALAR_W, 5)
+
+
+def scalar_init3d(phi0) -> np.ndarray:
+    """float32[7][nz][ny][nx]: lbm3d_scalar_begin."""
+    return _scalar_init(phi0, SCALAR_W3D, 7)
+
+
+def scalar_phi(g) -> np.ndarray:
+    """phi of every cell: the populations summed in speed order (either lattice)."""
+    g = np.asarray(g, np.float32)
+    phi = g[0]
+    for k in range(1, g.shape[0]):
+        phi = phi + g[k]
+    return phi
+
+
+scalar_phi3d = scalar_phi
+
+
+def _scalar_step(g, u, obst, omega_s, w, opp, speeds, c):
+    g = np.asarray(g, np.float32)
+    u = [np.asarray(a, np.float32) for a in u]
+    om, c = np.float32(omega_s), np.float32(c)
+    # p_k: what arrives along speed k, from the periodic neighbour against it
+    p = [g[0]] + [np.roll(g[k + 1], sign, axis=axis) for k, (_, axis, sign) in enumerate(speeds)]
+    phi = p[0]
+    for k in range(1, len(p)):
+        phi = phi + p[k]
+    t = phi * w[1]
+    a = [t * (c * uc) for uc in u]
+    e = [phi * w[0]] + [(t + a[comp]) if sign > 0 else (t - a[comp]) for comp, _, sign in speeds]
+    blocked = np.asarray(obst) != 0
+    return np.stack([np.where(blocked, p[opp[k]], p[k] + om * (e[k] - p[k])) for k in range(len(p))])
+
+
+def scalar_step(g, ux, uy, obst, omega_s) -> np.ndarray:
+    """One D2Q5 step over the frozen velocity field (lbm_scalar_advance(1) without the fixed list /
+    lbm_scalar_step_ref): ux, uy float32[ny][nx] as Engine.fields() gives them, obst [ny][nx]."""
+    return _scalar_step(g, (ux, uy), obst, omega_s, SCALAR_W, SCALAR_OPP, SCALAR_SPEEDS, 3)
+
+
+def scalar_step3d(g, ux, uy, uz, obst, omega_s) -> np.ndarray:
+    """One D3Q7 step (lbm3d_scalar_advance(1) / lbm3d_scalar_step_ref)."""
+    return _scalar_step(g, (ux, uy, uz), obst, omega_s, SCALAR_W3D, SCALAR_OPP3D, SCALAR_SPEEDS3D, 4)
+
+
+def _scalar_apply_fixed(g, idx, value, w):
+    g = np.array(g, np.float32)
+    value = np.asarray(value, np.float32).reshape(-1)
+    g[(0,) + idx] = value * w[0]
+    moving = value * w[1]
+    for k in range(1, g.shape[0]):
+        g[(k,) + idx] = moving
+    return g
+
+
+def scalar_apply_fixed(g, x, y, value) -> np.ndarray:
+    """A copy of g with the listed cells set to the begin state of `value` (lbm_scalar_set_fixed)."""
+    return _scalar_apply_fixed(g, (np.asarray(y, np.int64), np.asarray(x, np.int64)), value, SCALAR_W)
+
+
+def scalar_apply_fixed3d(g, x, y, z, value) -> np.ndarray:
+    return _scalar_apply_fixed(g, (np.asarray(z, np.int64), np.asarray(y, np.int64), np.asarray(x, np.int64)), value,
+                               SCALAR_W3D)
+
+
+def scalar_stats(g, obst):
+    """(total, min, max) of lbm_scalar_stats: the float64 sum of every cell's float32 phi (math.fsum:
+    the exact sum, which the device's fold approaches within its bound) and the extremes over the
+    fluid cells (+inf, -inf when there is none).  Either lattice."""
+    import math
+    phi = scalar_phi(g)
+    fluid = phi[np.asarray(obst) == 0]
+    total = math.fsum(phi.astype(np.float64).ravel().tolist())
+    return total, np.float32(fluid.min(initial=np.inf)), np.float32(fluid.max(initial=-np.inf))
+
+
+scalar_stats3d = scalar_stats
+
+
+def read_scalar_state(filename: str, nx: int, ny: int) -> np.ndarray:
+    """scalar_state.dat (`x y phi` per cell, phi in %.9g) -> float32[ny][nx]."""
+    phi = np.zeros((ny, nx), np.float32)
+    with open(filename, "r") as f:
+        for line in f:
+            t = line.split()
+            if t:
+                phi[int(t[1]), int(t[0])] = np.float32(t[2])
+    return phi
 
 
 def write_average_velocities(filename: str, av_vels) -> bool:

@@ -115,6 +115,15 @@ TRACER_BLOCK = 256                        # lanes (= points) per block of the tr
 # names of tracer_sample()'s arrays, in the argument order of lbm_tracer_sample / lbm3d_tracer_sample
 TRACER_FIELDS = ("ux", "uy", "pressure")
 TRACER_FIELDS3D = ("ux", "uy", "uz", "pressure")
+# every symbol include/lbm_scalar_hip.h declares (passive scalar: D2Q5 beside D2Q9, D3Q7 beside D3Q19)
+EXPORTED_SCALAR = [
+    "lbm_scalar_begin", "lbm_scalar_set_fixed", "lbm_scalar_advance", "lbm_scalar_steps", "lbm_scalar_store",
+    "lbm_scalar_stats", "lbm_scalar_end", "lbm_scalar_step_ref",
+    "lbm3d_scalar_begin", "lbm3d_scalar_set_fixed", "lbm3d_scalar_advance", "lbm3d_scalar_steps",
+    "lbm3d_scalar_store", "lbm3d_scalar_stats", "lbm3d_scalar_end", "lbm3d_scalar_step_ref",
+]
+SCALAR_MAX_PARTS = 16                     # LBM_SCALAR_MAX_PARTS
+SCALAR_Q, SCALAR_Q3D = 5, 7               # populations per cell of the scalar lattice
 Q3 = 19
 
 
@@ -335,6 +344,23 @@ def load_library() -> ctypes.CDLL:
                                      ctypes.c_int),
         "lbm3d_tracer_sample_ref": ([i32, i32, i32, f32p, f32p, f32p, f32p, i64, f64p, f64p, f64p,
                                      f64p, f64p, f64p, f64p], ctypes.c_int),
+        # include/lbm_scalar_hip.h
+        "lbm_scalar_begin": ([H, ctypes.c_float, f32p], ctypes.c_int),
+        "lbm_scalar_set_fixed": ([H, i64, i32p, i32p, f32p], ctypes.c_int),
+        "lbm_scalar_advance": ([H, i32], ctypes.c_int),
+        "lbm_scalar_steps": ([H, i64p], ctypes.c_int),
+        "lbm_scalar_store": ([H, f32p, f32p], ctypes.c_int),
+        "lbm_scalar_stats": ([H, f64p, f32p, f32p], ctypes.c_int),
+        "lbm_scalar_end": ([H], ctypes.c_int),
+        "lbm_scalar_step_ref": ([i32, i32, ctypes.c_float, f32p, f32p, u8p, f32p, f32p], ctypes.c_int),
+        "lbm3d_scalar_begin": ([H, ctypes.c_float, f32p], ctypes.c_int),
+        "lbm3d_scalar_set_fixed": ([H, i64, i32p, i32p, i32p, f32p], ctypes.c_int),
+        "lbm3d_scalar_advance": ([H, i32], ctypes.c_int),
+        "lbm3d_scalar_steps": ([H, i64p], ctypes.c_int),
+        "lbm3d_scalar_store": ([H, f32p, f32p], ctypes.c_int),
+        "lbm3d_scalar_stats": ([H, f64p, f32p, f32p], ctypes.c_int),
+        "lbm3d_scalar_end": ([H], ctypes.c_int),
+        "lbm3d_scalar_step_ref": ([i32, i32, i32, ctypes.c_float, f32p, f32p, f32p, u8p, f32p, f32p], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -453,6 +479,36 @@ def tracer_sample_ref(ux, uy, pressure, x, y):
 def tracer_sample3d_ref(ux, uy, uz, pressure, x, y, z):
     """The D3Q19 twin: lbm3d_tracer_sample_ref."""
     return _sample_ref(load_library().lbm3d_tracer_sample_ref, TRACER_FIELDS3D, (ux, uy, uz, pressure), (x, y, z))
+
+
+def scalar_step_ref(g, ux, uy, obst, omega_s):
+    """float32[5][ny][nx]: lbm_scalar_step_ref -- one step by the C++ per-cell function of the
+    kernel, compiled for the host (no GPU).  lio.scalar_step restates it."""
+    (ux, uy), (nx, ny) = _ref_fields((ux, uy), 2)
+    g = np.ascontiguousarray(g, np.float32)
+    obst = np.ascontiguousarray(obst, np.uint8)
+    if g.shape != (SCALAR_Q, ny, nx) or obst.shape != (ny, nx):
+        raise ValueError("g must be [5][ny][nx] and obst [ny][nx] of the fields' shape")
+    out = np.zeros_like(g)
+    rc = load_library().lbm_scalar_step_ref(nx, ny, float(omega_s), _ptr(ux), _ptr(uy), _ptr(obst), _ptr(g), _ptr(out))
+    if rc != LBM_OK:
+        raise LbmError(rc, "lbm_scalar_step_ref: invalid argument")
+    return out
+
+
+def scalar_step3d_ref(g, ux, uy, uz, obst, omega_s):
+    """float32[7][nz][ny][nx]: lbm3d_scalar_step_ref.  lio.scalar_step3d restates it."""
+    (ux, uy, uz), (nx, ny, nz) = _ref_fields((ux, uy, uz), 3)
+    g = np.ascontiguousarray(g, np.float32)
+    obst = np.ascontiguousarray(obst, np.uint8)
+    if g.shape != (SCALAR_Q3D, nz, ny, nx) or obst.shape != (nz, ny, nx):
+        raise ValueError("g must be [7][nz][ny][nx] and obst [nz][ny][nx] of the fields' shape")
+    out = np.zeros_like(g)
+    rc = load_library().lbm3d_scalar_step_ref(nx, ny, nz, float(omega_s), _ptr(ux), _ptr(uy), _ptr(uz), _ptr(obst),
+                                              _ptr(g), _ptr(out))
+    if rc != LBM_OK:
+        raise LbmError(rc, "lbm3d_scalar_step_ref: invalid argument")
+    return out
 
 
 def partition(nx: int, ny: int, parts: int, grid_rows: int = 0, grid_cols: int = 0):
@@ -894,7 +950,98 @@ class _Tracers:
         return out
 
 
-class Engine(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
+class _Scalar:
+    """Engine / Engine3D methods over include/lbm_scalar_hip.h; the class sets _SCALAR_Q."""
+
+    def scalar_begin(self, phi0=None, omega_s=None, diffusivity=None) -> None:
+        """Start (or restart) a passive scalar at phi0 (float32 array of the domain's shape; None:
+        zeros) with the relaxation rate omega_s in (0, 2) or the diffusivity D -- exactly one of the
+        two; D = (1 / omega_s - 1/2) / 3 in 2-D, / 4 in 3-D.  40 B (56 B) of device memory per cell."""
+        if (omega_s is None) == (diffusivity is None):
+            raise ValueError("give exactly one of omega_s and diffusivity")
+        dims = len(self._shape())
+        if omega_s is None:
+            if not float(diffusivity) > 0:
+                raise ValueError("diffusivity must be positive")
+            omega_s = 1.0 / ((3.0 if dims == 2 else 4.0) * float(diffusivity) + 0.5)
+        if phi0 is not None:
+            phi0 = np.ascontiguousarray(phi0, np.float32)
+            if phi0.shape != self._shape():
+                raise ValueError(f"phi0 must have the shape {self._shape()}")
+        self._check(self._fn("scalar_begin")(self._h, float(omega_s), None if phi0 is None else _ptr(phi0)))
+
+    def scalar_fix(self, x, y, *rest) -> None:
+        """scalar_fix(x, y[, z], value): replace the fixed list by these distinct cells, which hold the
+        begin state of `value` from now on (set now and again after every scalar step); empty arrays
+        clear the list."""
+        dims = len(self._shape())
+        if len(rest) != dims - 1:
+            raise ValueError(f"scalar_fix takes {dims} coordinate arrays and the values")
+        coords = [np.ascontiguousarray(c, np.int32).reshape(-1) for c in (x, y) + rest[:-1]]
+        value = np.ascontiguousarray(rest[-1], np.float32).reshape(-1)
+        if len({c.size for c in coords} | {value.size}) != 1:
+            raise ValueError("coordinate and value arrays must have one length")
+        self._check(self._fn("scalar_set_fixed")(self._h, value.size, *[_ptr(c) for c in coords], _ptr(value)))
+
+    def scalar_advance(self, n: int = 1) -> None:
+        """n scalar steps over the current, frozen lattice (nothing goes to the host): n times
+        lio.scalar_step[3d] of fields(), then the fixed list, bit for bit."""
+        self._check(self._fn("scalar_advance")(self._h, int(n)))
+
+    def scalar(self, populations: bool = False):
+        """phi (float32 array of the domain's shape), or (phi, g) with the planar populations
+        float32[5][ny][nx] / [7][nz][ny][nx]."""
+        phi = np.zeros(self._shape(), np.float32)
+        if not populations:
+            self._check(self._fn("scalar_store")(self._h, _ptr(phi), None))
+            return phi
+        g = np.zeros((self._SCALAR_Q,) + self._shape(), np.float32)
+        self._check(self._fn("scalar_store")(self._h, _ptr(phi), _ptr(g)))
+        return phi, g
+
+    def scalar_stats(self):
+        """(total, min, max): the fp64 sum of every cell's fp32 phi, folded in a fixed order, and the
+        extremes over the fluid cells (lbm_scalar_stats)."""
+        total, lo, hi = ctypes.c_double(), ctypes.c_float(), ctypes.c_float()
+        self._check(self._fn("scalar_stats")(self._h, ctypes.byref(total), ctypes.byref(lo), ctypes.byref(hi)))
+        return total.value, lo.value, hi.value
+
+    @property
+    def scalar_steps(self) -> int:
+        n = ctypes.c_int64()
+        self._check(self._fn("scalar_steps")(self._h, ctypes.byref(n)))
+        return n.value
+
+    def scalar_end(self) -> None:
+        """Free the scalar lattice (close() frees it too)."""
+        self._check(self._fn("scalar_end")(self._h))
+
+    def run_scalar(self, steps: int, stride: int = 1, accelerate_first: bool = False):
+        """Advance flow and scalar together: repeat "run_steps(stride), then scalar_advance(stride)"
+        (the remainder last; scalar_begin first).  stride = 1 is the exact coupling: every scalar
+        step sees the velocity of its own flow step.  A stride equal to the fused depth
+        (steps_per_launch()) keeps the flow on its fused launches, at the price of a velocity that
+        is frozen for that many scalar steps.  Returns the float32[steps] concatenation of the
+        chunks' average velocities (D3Q19: empty).  The flow is what run_steps in the same chunks
+        gives; chunking behaves as in run_averaged."""
+        return self._chunks(steps, stride, accelerate_first, True, lambda n, done: self.scalar_advance(n))
+
+    def scalar_history(self, steps: int, every: int, stride: int = 1, accelerate_first: bool = False):
+        """run_scalar(every, stride) chunk after chunk (the remainder last), scalar_stats() after
+        each: a list of (step, total, min, max).  accelerate_first applies to the first chunk (D2Q9)."""
+        steps, every = int(steps), int(every)
+        if steps < 0 or every < 1:
+            raise ValueError("steps >= 0 and every >= 1")
+        out, done = [], 0
+        while done < steps:
+            n = min(every, steps - done)
+            self.run_scalar(n, stride, accelerate_first and done == 0)
+            done += n
+            out.append((done,) + self.scalar_stats())
+        return out
+
+
+class Engine(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers, _Scalar):
     """One lbm_handle: the HIP counterpart of the reference's poplar::Engine."""
 
     _PREFIX = "lbm_"
@@ -903,6 +1050,7 @@ class Engine(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tra
     _STRESS_FIELDS = STRESS_FIELDS
     _BIN_FIELDS = BIN_FIELDS
     _TRACER_FIELDS = TRACER_FIELDS
+    _SCALAR_Q = SCALAR_Q
 
     def __init__(self, params, obstacles: np.ndarray, num_gpus: int = 1, *, parts: int | None = None,
                  grid=(0, 0), transport: int = TRANSPORT_LOCAL, rank: int = 0, world: int = 1,
@@ -1114,7 +1262,7 @@ class Engine(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tra
         return "tolerance" if int(self._L.lbm_numerics(self._h)) == 1 else "bitwise"
 
 
-class Engine3D(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers):
+class Engine3D(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers, _Scalar):
     """One lbm3d_handle: the D3Q19 extension engine (include/lbm3d_hip.h)."""
 
     _PREFIX = "lbm3d_"
@@ -1123,6 +1271,7 @@ class Engine3D(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _T
     _STRESS_FIELDS = STRESS_FIELDS3D
     _BIN_FIELDS = BIN_FIELDS3D
     _TRACER_FIELDS = TRACER_FIELDS3D
+    _SCALAR_Q = SCALAR_Q3D
 
     def __init__(self, params, obstacles: np.ndarray, *, parts: int = 1, transport: int = TRANSPORT_LOCAL,
                  rank: int = 0, world: int = 1, devices=None, unique_id: bytes | None = None, flags: int = 0):
