@@ -69,8 +69,12 @@
  * LBM_SCALAR_MAX_PARTS local sub-domains, or on a handle that does not hold
  * the whole domain (begin: LBM_E_INVALID with a message); several scalar
  * steps per launch; caching the velocity across the sub-steps of a frozen
- * lattice; Dirichlet or flux wall models beyond the fixed list; buoyancy (any
- * feedback on the flow); time averages of the scalar.
+ * lattice; Dirichlet or flux wall models beyond the fixed list; time averages
+ * of the scalar.
+ *
+ * Feedback on the flow: lbm_thermal_hip.h (included below) adds the Boussinesq
+ * buoyancy calls lbm_scalar_buoyancy / lbm3d_scalar_buoyancy, the one place
+ * where a scalar call writes the flow lattice.
  */
 #ifndef LBM_SCALAR_HIP_H
 #define LBM_SCALAR_HIP_H
@@ -143,5 +147,7 @@ int lbm3d_scalar_step_ref(int32_t nx, int32_t ny, int32_t nz, float omega_s, con
 #ifdef __cplusplus
 }
 #endif
+
+#include "lbm_thermal_hip.h"
 
 #endif /* LBM_SCALAR_HIP_H */

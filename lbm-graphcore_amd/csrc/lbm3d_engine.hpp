@@ -237,6 +237,9 @@ struct lbm3d_handle {
     void destroy();
     // lbm3d_fields.hip
     lbm::Box3View box_view(const lbm::Slab &s, int x0, int y0, int z0, int bx, int by, int bz) const;
+    lbm::Box3Edit slab_edit(const lbm::Slab &s) const {  // every cell of the slab, writable
+        return lbm::Box3Edit{box_view(s, 0, 0, 0, p.nx, p.ny, s.nzs), s.o[s.cur]};
+    }
     void check_box(const lbm3d_box &b) const;
     bool slab_planes(const lbm::Slab &s, const lbm3d_box &b, int &zlo, int &zhi) const;
     // where the box's planes from global plane zlo on lie in a packed host array float[b.nz][b.ny][b.nx]
@@ -296,4 +299,5 @@ struct lbm3d_handle {
     void scalar_store(float *phi, float *g);
     void scalar_stats(double *total, float *min, float *max);
     void scalar_end();
+    void scalar_buoyancy(float sx, float sy, float sz, float phi_ref);  // include/lbm_thermal_hip.h
 };

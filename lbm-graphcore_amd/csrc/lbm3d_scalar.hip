@@ -1,7 +1,8 @@
 // lbm3d_scalar.hip -- the passive scalar of the D3Q19 engine (the
-// lbm3d_scalar_* functions of include/lbm_scalar_hip.h): the D3Q7 step kernel
-// over the lattice of one z slab, the engine's host side, the extern "C"
-// functions and the host-only restatement lbm3d_scalar_step_ref.
+// lbm3d_scalar_* functions of include/lbm_scalar_hip.h and lbm_thermal_hip.h):
+// the D3Q7 step kernel over the lattice of one z slab, the buoyancy kick on
+// that lattice, the engine's host side, the extern "C" functions and the
+// host-only restatements lbm3d_scalar_step_ref and lbm3d_scalar_buoyancy_ref.
 //
 // The step kernel.  Memory-bound: per cell it must move 76 B of flow
 // populations, the obstacle byte, 28 B of scalar populations read and 28 B
@@ -159,9 +160,113 @@ __global__ __launch_bounds__(S3X *S3Y) void scalar_step3d(Step3 a) {
     }
 }
 
+// ---- the buoyancy kick (include/lbm_thermal_hip.h) ----
+//
+// A streaming read-modify-write of the current flow lattice: per cell 28 B of
+// scalar populations and the obstacle byte read, the eighteen moving flow
+// planes read and written (173 B; f0 is not touched).  The block and grid of
+// the step kernel.  On the quad path a lane first forms the nine increments of
+// each of its four cells from the seven scalar planes, then walks the nine
+// opposite pairs of flow planes three at a time: six 16-B loads, then six
+// 16-B stores (the 25 quads are never live together).  A lane needs only its own cells and
+// owns what it writes: no LDS, no atomics, no cross-lane move, no race in
+// place.  Ghost planes and pad columns are not touched.
+
+// all cells of one slab, writable, its first plane in the domain, and the current scalar set
+constexpr int KICK3_BATCH = 3;  // pairs loaded together; divides KICK3_PAIRS
+static_assert(KICK3_PAIRS % KICK3_BATCH == 0, "whole batches");
+
+struct Kick3 : Box3Edit {
+    const float *g;
+    long long gplane;
+    int gsp, gz0;
+    float kx, ky, kz, phi_ref;
+};
+
 namespace {
 
-dim3 step3d_grid(const Step3 &a) {
+__device__ __forceinline__ void kick_one(const Kick3 &a, int x, int y, int z) {
+    const long long at = ((long long)(a.gz0 + z) * a.ny + y) * a.gsp + x;
+    float g[7];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) g[k] = a.g[k * a.gplane + at];
+    const bool blocked = a.obst[((long long)z * a.ny + y) * a.nx + x] != 0;
+    float inc[KICK3_PAIRS];
+    kick3_inc(cell_phi<7>(g), a.phi_ref, a.kx, a.ky, a.kz, inc);
+    float *f = a.e + (long long)z * a.PL + (long long)y * a.px + x;
+#pragma unroll
+    for (int j = 0; j < KICK3_PAIRS; ++j) {
+        float *fp = f + kick3_plus(j) * a.KS, *fm = f + kick3_minus(j) * a.KS;
+        float plus = *fp, minus = *fm;
+        kick_pair(plus, minus, blocked, inc[j]);
+        *fp = plus;
+        *fm = minus;
+    }
+}
+
+__device__ __forceinline__ float4 quad_of(const float (&c)[4]) { return make_float4(c[0], c[1], c[2], c[3]); }
+
+}  // namespace
+
+__global__ __launch_bounds__(S3X *S3Y) void scalar_buoyancy3d(Kick3 a) {
+    const bool quad = a.quad != 0;
+    const int cpl = quad ? 4 : 1;  // cells per lane
+    const int tx = threadIdx.x & (S3X - 1), ty = threadIdx.x / S3X;
+    const int x = (blockIdx.x * S3X + tx) * cpl;
+    if (x >= a.bx) return;
+    const bool full = quad && x + 4 <= a.bx;
+    const bool obst_word = (a.nx & 3) == 0;
+    for (int z = blockIdx.z; z < a.bz; z += gridDim.z) {
+        for (int y = blockIdx.y * S3Y + ty; y < a.by; y += gridDim.y * S3Y) {
+            if (full) {
+                float inc[4][KICK3_PAIRS];
+                unsigned bits;
+                {
+                    float4 gq[7];
+                    load_quad<7, true>(a.g + ((long long)(a.gz0 + z) * a.ny + y) * a.gsp + x, a.gplane, gq);
+                    bits = quad_map_bytes(a.obst + ((long long)z * a.ny + y) * a.nx + x, obst_word);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float g[7] = {pick(gq[0], i), pick(gq[1], i), pick(gq[2], i), pick(gq[3], i),
+                                            pick(gq[4], i), pick(gq[5], i), pick(gq[6], i)};
+                        kick3_inc(cell_phi<7>(g), a.phi_ref, a.kx, a.ky, a.kz, inc[i]);
+                    }
+                }
+                float *f = a.e + (long long)z * a.PL + (long long)y * a.px + x;
+                // three pairs at a time: six 16-B loads in flight, then their six stores (a store ends the run
+                // of loads the compiler may issue ahead of it: the planes may alias for all it knows)
+#pragma unroll
+                for (int j0 = 0; j0 < KICK3_PAIRS; j0 += KICK3_BATCH) {
+                    float4 vp[KICK3_BATCH], vm[KICK3_BATCH];
+#pragma unroll
+                    for (int j = 0; j < KICK3_BATCH; ++j) {
+                        vp[j] = *reinterpret_cast<const float4 *>(f + kick3_plus(j0 + j) * a.KS);
+                        vm[j] = *reinterpret_cast<const float4 *>(f + kick3_minus(j0 + j) * a.KS);
+                    }
+#pragma unroll
+                    for (int j = 0; j < KICK3_BATCH; ++j) {
+                        float plus[4] = {vp[j].x, vp[j].y, vp[j].z, vp[j].w};
+                        float minus[4] = {vm[j].x, vm[j].y, vm[j].z, vm[j].w};
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            kick_pair(plus[i], minus[i], ((bits >> (8 * i)) & 0xffu) != 0, inc[i][j0 + j]);
+                        *reinterpret_cast<float4 *>(f + kick3_plus(j0 + j) * a.KS) = quad_of(plus);
+                        *reinterpret_cast<float4 *>(f + kick3_minus(j0 + j) * a.KS) = quad_of(minus);
+                    }
+                }
+            } else {
+                // one cell per lane, or the ragged tail of a row: its last nx % 4 cells, one at a time
+#pragma unroll 1
+                for (int i = 0; i < cpl && x + i < a.bx; ++i) kick_one(a, x + i, y, z);
+            }
+        }
+    }
+}
+
+namespace {
+
+// the grid of both kernels over a whole-slab view
+dim3 slab_grid(const Box3View &a) {
     const int cpl = a.quad ? 4 : 1;
     const long long lanes = ((long long)a.bx + cpl - 1) / cpl;
     const long long gx = (lanes + S3X - 1) / S3X;
@@ -235,7 +340,7 @@ void lbm3d_handle::scalar_advance(int steps) {
             a.gz0 = s.z0;
             a.nz = p.nz;
             a.omega = t.omega;
-            hipLaunchKernelGGL(scalar::scalar_step3d, scalar::step3d_grid(a), dim3(scalar::S3X * scalar::S3Y), 0, st, a);
+            hipLaunchKernelGGL(scalar::scalar_step3d, scalar::slab_grid(a), dim3(scalar::S3X * scalar::S3Y), 0, st, a);
             HIP_CHECK(hipGetLastError());
         }
         t.cur ^= 1;
@@ -268,6 +373,33 @@ void lbm3d_handle::scalar_stats(double *total, float *min, float *max) {
 }
 
 void lbm3d_handle::scalar_end() { scalar::end(scalars); }
+
+// The kick on the current lattice of every slab, then the ghost planes as after load_cells (refresh).
+void lbm3d_handle::scalar_buoyancy(float sx, float sy, float sz, float phi_ref) {
+    scalar::State &t = scalar_state(*this);
+    if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice for the scalar to act on");
+    if (!(std::isfinite(sx) && std::isfinite(sy) && std::isfinite(sz) && std::isfinite(phi_ref)))
+        throw lbm_failure(LBM_E_INVALID, "the impulse and phi_ref must be finite");
+    if (sx == 0.f && sy == 0.f && sz == 0.f) return;
+    sync_all();
+    HIP_CHECK(hipSetDevice(slabs[0].dev));
+    const hipStream_t st = slabs[0].s_comp;
+    for (const auto &s : slabs) {
+        scalar::Kick3 a{slab_edit(s)};
+        a.g = t.g[t.cur];
+        a.gplane = t.grid.plane;
+        a.gsp = t.grid.sp;
+        a.gz0 = s.z0;
+        a.kx = p.density * sx;
+        a.ky = p.density * sy;
+        a.kz = p.density * sz;
+        a.phi_ref = phi_ref;
+        hipLaunchKernelGGL(scalar::scalar_buoyancy3d, scalar::slab_grid(a), dim3(scalar::S3X * scalar::S3Y), 0, st, a);
+        HIP_CHECK(hipGetLastError());
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    refresh();
+}
 
 // ---- C ABI and the host-only restatement ----
 
@@ -329,6 +461,29 @@ int lbm3d_scalar_step_ref(int32_t nx, int32_t ny, int32_t nz, float omega_s, con
                 scalar::cell3(p, obst[i] != 0, ux[i], uy[i], uz[i], omega_s, out);
                 for (int k = 0; k < 7; ++k) g_out[k * plane + i] = out[k];
             }
+    return LBM_OK;
+}
+
+int lbm3d_scalar_buoyancy(lbm3d_handle *h, float sx, float sy, float sz, float phi_ref) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->scalar_buoyancy(sx, sy, sz, phi_ref); });
+}
+
+int lbm3d_scalar_buoyancy_ref(int32_t nx, int32_t ny, int32_t nz, float density, float sx, float sy, float sz,
+                              float phi_ref, const uint8_t *obst, const float *g, float *cells) {
+    if (!scalar::kick_args_ok(nx, ny, nz, {density, sx, sy, sz, phi_ref}, {obst, g, cells})) return LBM_E_INVALID;
+    if (sx == 0.f && sy == 0.f && sz == 0.f) return LBM_OK;
+    const float kx = density * sx, ky = density * sy, kz = density * sz;
+    const size_t plane = (size_t)nx * ny * nz;
+    for (size_t i = 0; i < plane; ++i) {
+        float gc[7];
+        for (int k = 0; k < 7; ++k) gc[k] = g[k * plane + i];
+        float inc[scalar::KICK3_PAIRS];
+        scalar::kick3_inc(scalar::cell_phi<7>(gc), phi_ref, kx, ky, kz, inc);
+        float *c = cells + i * scalar::S3Q;
+        for (int j = 0; j < scalar::KICK3_PAIRS; ++j)
+            scalar::kick_pair(c[scalar::kick3_plus(j)], c[scalar::kick3_minus(j)], obst[i] != 0, inc[j]);
+    }
     return LBM_OK;
 }
 

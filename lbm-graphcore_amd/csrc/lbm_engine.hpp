@@ -424,6 +424,7 @@ struct lbm_handle {
     // diagnostics (lbm_diag_host.hpp): the current lattice of a sub-domain, and where its rows lie in a
     // planar host array -- at its rectangle of [ny][nx], or (local) packed after the `packed` cells before it
     LatticeView lattice_view(const Sub &s) const;
+    LatticeEdit lattice_edit(const Sub &s) const { return LatticeEdit{lattice_view(s), s.o[s.cur]}; }  // writable
     HostSpan host_span(const Sub &s, bool local, size_t packed) const {
         return local ? HostSpan{packed, (size_t)s.w} : HostSpan{(size_t)s.rect.y0 * p.nx + s.rect.x0, (size_t)p.nx};
     }
@@ -480,5 +481,6 @@ struct lbm_handle {
     void scalar_store(float *phi, float *g);
     void scalar_stats(double *total, float *min, float *max);
     void scalar_end();
+    void scalar_buoyancy(float sx, float sy, float phi_ref);  // include/lbm_thermal_hip.h
     void destroy();
 };

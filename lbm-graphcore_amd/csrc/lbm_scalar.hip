@@ -1,7 +1,8 @@
 // lbm_scalar.hip -- the passive scalar of the D2Q9 engine (the lbm_scalar_*
-// functions of include/lbm_scalar_hip.h): the D2Q5 step kernel over the
-// lattice of one sub-domain, the engine's host side, the extern "C" functions
-// and the host-only restatement lbm_scalar_step_ref.
+// functions of include/lbm_scalar_hip.h and lbm_thermal_hip.h): the D2Q5 step
+// kernel over the lattice of one sub-domain, the buoyancy kick on that
+// lattice, the engine's host side, the extern "C" functions and the host-only
+// restatements lbm_scalar_step_ref and lbm_scalar_buoyancy_ref.
 //
 // The step kernel.  Memory-bound: per cell it must move 36 B of flow
 // populations, the obstacle byte, 20 B of scalar populations read and 20 B
@@ -135,6 +136,89 @@ __global__ __launch_bounds__(BLOCK) void scalar_step(Step2 a) {
     }
 }
 
+// ---- the buoyancy kick (include/lbm_thermal_hip.h) ----
+//
+// A streaming read-modify-write of the current flow lattice: per cell 20 B of
+// scalar populations and the obstacle byte read, the eight moving flow planes
+// read and written (85 B; f0 is not touched).  The scalar step's shape: four
+// consecutive cells per lane, 16-B loads and stores on both lattices, the
+// ragged tail and sub-domains off the alignment one cell at a time.  A lane
+// needs only its own cells and owns what it writes: no LDS, no atomics, no
+// cross-lane move, no race in place.  Ghost cells and pad columns are not
+// touched.
+
+// one sub-domain's flow lattice, writable, where its cell (0, 0) lies in the domain, and the current scalar set
+struct Kick2 : LatticeEdit {
+    const float *g;
+    long long gplane;
+    int gsp, gx0, gy0;
+    int quad;  // gx0 % 4 == 0: the 16-B path
+    float kx, ky, phi_ref;
+};
+
+namespace {
+
+__device__ __forceinline__ void kick_one(const Kick2 &a, int x, int y) {
+    const long long at = (long long)(a.gy0 + y) * a.gsp + (a.gx0 + x);
+    float g[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) g[k] = a.g[k * a.gplane + at];
+    const bool blocked = a.obst[(long long)y * a.w + x] != 0;
+    float inc[KICK2_PAIRS];
+    kick2_inc(cell_phi<5>(g), a.phi_ref, a.kx, a.ky, inc);
+    float *f = a.e + (long long)y * a.pitch + x;
+#pragma unroll
+    for (int j = 0; j < KICK2_PAIRS; ++j) {
+        float *fp = f + kick2_plus(j) * a.plane, *fm = f + kick2_minus(j) * a.plane;
+        float plus = *fp, minus = *fm;
+        kick_pair(plus, minus, blocked, inc[j]);
+        *fp = plus;
+        *fm = minus;
+    }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(BLOCK) void scalar_buoyancy(Kick2 a) {
+    const int qpr = (a.w + 3) >> 2;  // lanes' quads per row
+    const long long total = (long long)qpr * a.h;
+    const bool obst_word = (a.w & 3) == 0;
+    for (long long q = (long long)blockIdx.x * BLOCK + threadIdx.x; q < total; q += (long long)gridDim.x * BLOCK) {
+        const int y = (int)(q / qpr);
+        const int x = (int)(q - (long long)y * qpr) << 2;
+        if (a.quad && x + 4 <= a.w) {
+            float4 gq[5];
+            load_quad<5>(a.g + (long long)(a.gy0 + y) * a.gsp + (a.gx0 + x), a.gplane, gq);
+            const unsigned bits = quad_map_bytes(a.obst + (long long)y * a.w + x, obst_word);
+            float *f = a.e + (long long)y * a.pitch + x;
+            float4 v[Q];  // v[0] stays unused: the rest speed is neither loaded nor stored
+#pragma unroll
+            for (int k = 1; k < Q; ++k) v[k] = *reinterpret_cast<const float4 *>(f + k * a.plane);
+            float o[Q][4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float g[5] = {pick(gq[0], i), pick(gq[1], i), pick(gq[2], i), pick(gq[3], i), pick(gq[4], i)};
+                const bool blocked = ((bits >> (8 * i)) & 0xffu) != 0;
+                float inc[KICK2_PAIRS];
+                kick2_inc(cell_phi<5>(g), a.phi_ref, a.kx, a.ky, inc);
+#pragma unroll
+                for (int j = 0; j < KICK2_PAIRS; ++j) {
+                    float plus = pick(v[kick2_plus(j)], i), minus = pick(v[kick2_minus(j)], i);
+                    kick_pair(plus, minus, blocked, inc[j]);
+                    o[kick2_plus(j)][i] = plus;
+                    o[kick2_minus(j)][i] = minus;
+                }
+            }
+#pragma unroll
+            for (int k = 1; k < Q; ++k)
+                *reinterpret_cast<float4 *>(f + k * a.plane) = make_float4(o[k][0], o[k][1], o[k][2], o[k][3]);
+        } else {
+            // the ragged tail of a row, or a sub-domain off the alignment: one cell at a time
+            for (int i = 0; i < 4 && x + i < a.w; ++i) kick_one(a, x + i, y);
+        }
+    }
+}
+
 }  // namespace scalar
 }  // namespace lbm
 
@@ -243,6 +327,40 @@ void lbm_handle::scalar_stats(double *total, float *min, float *max) {
 
 void lbm_handle::scalar_end() { scalar::end(scalars); }
 
+// The kick on the current lattice of every sub-domain.  The ghost ring is left to the next run, which rebuilds
+// it first (ring_stale), as it does after a run that ended on a remainder launch; the resident kernel keeps none,
+// the pipeline rebuilds its own every step, and no diagnostic reads a ghost cell.
+void lbm_handle::scalar_buoyancy(float sx, float sy, float phi_ref) {
+    scalar::State &t = scalar_state(*this);
+    if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice for the scalar to act on");
+    if (!(std::isfinite(sx) && std::isfinite(sy) && std::isfinite(phi_ref)))
+        throw lbm_failure(LBM_E_INVALID, "the impulse and phi_ref must be finite");
+    if (sx == 0.f && sy == 0.f) return;
+    sync_all();
+    prof_drop();
+    const Sub &s0 = subs[0];
+    set_device(s0);
+    for (const auto &s : subs) {
+        scalar::Kick2 a{lattice_edit(s)};
+        a.g = t.g[t.cur];
+        a.gplane = t.grid.plane;
+        a.gsp = t.grid.sp;
+        a.gx0 = s.rect.x0;
+        a.gy0 = s.rect.y0;
+        a.quad = s.rect.x0 % 4 == 0 ? 1 : 0;
+        a.kx = p.density * sx;
+        a.ky = p.density * sy;
+        a.phi_ref = phi_ref;
+        timed(s0, s0.s_comp, "scalar_buoyancy", [&] {
+            hipLaunchKernelGGL(scalar::scalar_buoyancy, dim3(fields_blocks(s.w, s.h)), dim3(BLOCK), 0, s0.s_comp, a);
+            HIP_CHECK(hipGetLastError());
+        });
+    }
+    ring_stale = true;
+    HIP_CHECK(hipStreamSynchronize(s0.s_comp));
+    prof_collect();
+}
+
 // ---- C ABI and the host-only restatement ----
 
 extern "C" {
@@ -297,6 +415,28 @@ int lbm_scalar_step_ref(int32_t nx, int32_t ny, float omega_s, const float *ux, 
             scalar::cell2(p, obst[i] != 0, ux[i], uy[i], omega_s, out);
             for (int k = 0; k < 5; ++k) g_out[k * plane + i] = out[k];
         }
+    return LBM_OK;
+}
+
+int lbm_scalar_buoyancy(lbm_handle *h, float sx, float sy, float phi_ref) {
+    if (!h) return LBM_E_INVALID;
+    return guarded(h, [&] { h->scalar_buoyancy(sx, sy, phi_ref); });
+}
+
+int lbm_scalar_buoyancy_ref(int32_t nx, int32_t ny, float density, float sx, float sy, float phi_ref,
+                            const uint8_t *obst, const float *g, float *cells) {
+    if (!scalar::kick_args_ok(nx, ny, 1, {density, sx, sy, phi_ref}, {obst, g, cells})) return LBM_E_INVALID;
+    if (sx == 0.f && sy == 0.f) return LBM_OK;
+    const float kx = density * sx, ky = density * sy;
+    const size_t plane = (size_t)nx * ny;
+    for (size_t i = 0; i < plane; ++i) {
+        const float gc[5] = {g[i], g[plane + i], g[2 * plane + i], g[3 * plane + i], g[4 * plane + i]};
+        float inc[scalar::KICK2_PAIRS];
+        scalar::kick2_inc(scalar::cell_phi<5>(gc), phi_ref, kx, ky, inc);
+        float *c = cells + i * Q;
+        for (int j = 0; j < scalar::KICK2_PAIRS; ++j)
+            scalar::kick_pair(c[scalar::kick2_plus(j)], c[scalar::kick2_minus(j)], obst[i] != 0, inc[j]);
+    }
     return LBM_OK;
 }
 

@@ -1,5 +1,6 @@
 // lbm_scalar.hpp -- the passive scalar of both engines (lbm_scalar.hip,
-// lbm3d_scalar.hip; include/lbm_scalar_hip.h): the per-cell arithmetic,
+// lbm3d_scalar.hip; include/lbm_scalar_hip.h) and its buoyancy kick on the
+// flow (include/lbm_thermal_hip.h): the per-cell arithmetic,
 // compiled for the device and for the host from one text, the scalar lattice a
 // handle keeps, the small kernels both engines share (fixed cells, phi,
 // statistics) and their host side.  The step kernels, which read the flow
@@ -78,6 +79,72 @@ LBM_HD void cell3(const float (&p)[7], bool blocked, float ux, float uy, float u
 
 LBM_HD int below(int c, int n) { return c == 0 ? n - 1 : c - 1; }
 LBM_HD int above(int c, int n) { return c + 1 == n ? 0 : c + 1; }
+
+// ---- the buoyancy kick (include/lbm_thermal_hip.h), host and device ----
+//
+// Per opposite pair of flow speeds one increment: added to the first speed of the pair, subtracted from the
+// second.  The pairs, in the order of the increments kick2_inc / kick3_inc form:
+constexpr int KICK2_PAIRS = 4, KICK3_PAIRS = 9;
+LBM_HD int kick2_plus(int j) {
+    constexpr int t[KICK2_PAIRS] = {1, 2, 5, 6};
+    return t[j];
+}
+LBM_HD int kick2_minus(int j) {
+    constexpr int t[KICK2_PAIRS] = {3, 4, 7, 8};
+    return t[j];
+}
+LBM_HD int kick3_plus(int j) {
+    constexpr int t[KICK3_PAIRS] = {1, 3, 9, 5, 7, 10, 11, 12, 13};
+    return t[j];
+}
+LBM_HD int kick3_minus(int j) {
+    constexpr int t[KICK3_PAIRS] = {2, 4, 14, 6, 8, 15, 16, 17, 18};
+    return t[j];
+}
+
+// the scalar of a cell: its Q stored populations summed in speed order
+template <int Q>
+LBM_HD float cell_phi(const float (&g)[Q]) {
+    float phi = g[0];
+#pragma unroll
+    for (int k = 1; k < Q; ++k) phi += g[k];
+    return phi;
+}
+
+// D2Q9: E/W, N/S, NE/SW, NW/SE
+LBM_HD void kick2_inc(float phi, float phi_ref, float kx, float ky, float (&inc)[KICK2_PAIRS]) {
+    const float d = phi - phi_ref;
+    const float jx = kx * d, jy = ky * d;
+    inc[0] = jx * (1.f / 3.f);
+    inc[1] = jy * (1.f / 3.f);
+    const float bx = jx * (1.f / 12.f), by = jy * (1.f / 12.f);
+    inc[2] = bx + by;
+    inc[3] = by - bx;
+}
+
+// D3Q19: +-x, +-y, +-z, then the six diagonal pairs in the order of kick3_plus
+LBM_HD void kick3_inc(float phi, float phi_ref, float kx, float ky, float kz, float (&inc)[KICK3_PAIRS]) {
+    const float d = phi - phi_ref;
+    const float jx = kx * d, jy = ky * d, jz = kz * d;
+    inc[0] = jx * (1.f / 6.f);
+    inc[1] = jy * (1.f / 6.f);
+    inc[2] = jz * (1.f / 6.f);
+    const float bx = jx * (1.f / 12.f), by = jy * (1.f / 12.f), bz = jz * (1.f / 12.f);
+    inc[3] = bx + by;
+    inc[4] = bx - by;
+    inc[5] = bx + bz;
+    inc[6] = bz - bx;
+    inc[7] = by + bz;
+    inc[8] = bz - by;
+}
+
+// One pair of one cell.  A select of the loaded value, not an added zero: an obstacle cell keeps its bits
+// (-0.f + 0.f is +0.f), and a branch here would sink the 16-B loads into it.
+LBM_HD void kick_pair(float &plus, float &minus, bool blocked, float inc) {
+    const float up = plus + inc, down = minus - inc;
+    plus = blocked ? plus : up;
+    minus = blocked ? minus : down;
+}
 
 // ---- the scalar lattice of a handle ----
 
@@ -335,6 +402,17 @@ inline void stats_out(const double (&sum)[1], const float (&m)[2], double *total
 // the *_ref entry points
 inline bool ref_args_ok(int nx, int ny, int nz, float omega, std::initializer_list<const void *> arrays) {
     if (nx < 1 || ny < 1 || nz < 1 || !(std::isfinite(omega) && omega > 0.f && omega < 2.f)) return false;
+    for (const void *p : arrays)
+        if (!p) return false;
+    return true;
+}
+
+// the *_buoyancy_ref entry points
+inline bool kick_args_ok(int nx, int ny, int nz, std::initializer_list<float> numbers,
+                         std::initializer_list<const void *> arrays) {
+    if (nx < 1 || ny < 1 || nz < 1) return false;
+    for (float v : numbers)
+        if (!std::isfinite(v)) return false;
     for (const void *p : arrays)
         if (!p) return false;
     return true;

@@ -5,7 +5,8 @@
 //              [--runs 5] [--kernel auto|resident|stream|step2|vec4|scalar|pipeline] [--spl S] [--out-dir DIR]
 //              [--tolerance] [--device-fields] [--forces] [--mean-every N] [--gradients] [--stress] [--binned BWxBH]
 //              [--tracers FILE [--trace-every N] [--trace-scheme euler|heun]]
-//              [--scalar FILE [--scalar-omega W] [--scalar-stride N]] [--json FILE]
+//              [--scalar FILE [--scalar-omega W] [--scalar-stride N] [--buoyancy GX,GY] [--scalar-ref R]]
+//              [--json FILE]
 //
 // Flow (same program numbering as the reference):
 //   load params/obstacles -> initialise cells on host -> create engine
@@ -59,11 +60,15 @@
 // then as many scalar steps over the frozen lattice, repeated -- and writes
 // scalar_state.dat after the run: `x y phi` per cell, x fastest, phi in %.9g
 // (lbm_scalar_hip.h).  GPU only.
+// --buoyancy GX,GY (with --scalar) lets the scalar drive the flow: ahead of
+// every chunk of n <= --scalar-stride steps the momentum
+// density * n * (GX, GY) * (phi - R) is added to every fluid cell, R from
+// --scalar-ref (default 0) (lbm_thermal_hip.h: lbm_scalar_buoyancy).
 // --device loopback places all N sub-domains on GPU 0 (the emulator analogue
 // of --device ipumodel: exercises the multi-GPU halo path on one device).
 // --device cpu runs the same fused step on the host's cores (lbm_cpu.hpp:
 // OpenMP rows, bitwise equal to the GPU engine's default numerics); the
-// GPU-only options (-n, --tolerance, --kernel, --spl, --graph-steps, --device-fields, --mean-every, --scalar) do not
+// GPU-only options (-n, --tolerance, --kernel, --spl, --graph-steps, --device-fields, --mean-every, --scalar, --buoyancy) do not
 // apply there and are refused with a message.
 #include <algorithm>
 #include <cstdio>
@@ -129,6 +134,9 @@ void usage(const char *exe) {
               << "                       diffusivity is (1/arg - 1/2) / 3)\n"
               << "      --scalar-stride arg  flow steps between two updates of the scalar, which then advances as many\n"
               << "                       steps over the frozen flow (default: 1, the exact coupling)\n"
+              << "      --buoyancy arg   GX,GY: with --scalar, the scalar drives the flow -- ahead of every chunk of n steps\n"
+              << "                       each fluid cell gains the momentum density * n * (GX, GY) * (phi - ref)\n"
+              << "      --scalar-ref arg the ref of --buoyancy (default: 0)\n"
               << "      --out-dir arg    directory for av_vels.dat / final_state.dat (default: .)\n"
               << "      --graph-steps arg  replay the step loop as hipGraphs of 2*arg launches (0 = library default, <0 = off)\n"
               << "      --dump-partitioning arg  write the sub-domain decomposition as JSON\n"
@@ -243,6 +251,9 @@ int main(int argc, char *argv[]) {
     std::string scalarFile;
     float scalarOmega = 1.0f;
     int scalarStride = 1;
+    bool buoyant = false, scalarRefGiven = false;
+    double buoyancyX = 0.0, buoyancyY = 0.0;
+    float scalarRef = 0.f;
     std::vector<std::string> gpuOnly;  // GPU-only options given on the command line
     int spl = 0;
     int numGpus = 1, runs = 5, graphSteps = 0, meanEvery = 0, binW = 0, binH = 0;
@@ -333,6 +344,19 @@ int main(int argc, char *argv[]) {
             scalarStride = std::atoi(v.c_str());
             if (scalarStride < 1) { usage(argv[0]); return EXIT_FAILURE; }
             gpuOnly.push_back(a);
+        } else if (a == "--buoyancy") {
+            char tail = 0;
+            if (!next(v) || sscanf(v.c_str(), "%lf,%lf%c", &buoyancyX, &buoyancyY, &tail) != 2) {
+                usage(argv[0]);
+                return EXIT_FAILURE;
+            }
+            buoyant = true;
+            gpuOnly.push_back(a);
+        } else if (a == "--scalar-ref") {
+            if (!next(v)) { usage(argv[0]); return EXIT_FAILURE; }
+            scalarRef = std::strtof(v.c_str(), nullptr);
+            scalarRefGiven = true;
+            gpuOnly.push_back(a);
         } else if (a == "--out-dir") {
             if (!next(outDir)) { usage(argv[0]); return EXIT_FAILURE; }
         } else if (a == "--graph-steps") {
@@ -383,6 +407,10 @@ int main(int argc, char *argv[]) {
         }
         tracers = lbmhost::readTracers(tracersFile, *params);
         if (!tracers.has_value()) return EXIT_FAILURE;
+    }
+    if ((buoyant || scalarRefGiven) && scalarFile.empty()) {
+        std::cerr << "--buoyancy and --scalar-ref act on the scalar of --scalar FILE: give it too" << std::endl;
+        return EXIT_FAILURE;
     }
     // --scalar: phi0 of every cell and the fixed list
     std::vector<float> scalarPhi, scalarFixedValue;
@@ -542,6 +570,9 @@ int main(int argc, char *argv[]) {
                            h, "lbm_scalar_set_fixed");
             for (int done = 0; done < (int)params->maxIters;) {
                 const int n = std::min(scalarStride, (int)params->maxIters - done);
+                if (buoyant)  // the impulse of the chunk's n steps at once
+                    lbmhost::check(lbm_scalar_buoyancy(h, (float)(n * buoyancyX), (float)(n * buoyancyY), scalarRef), h,
+                                   "lbm_scalar_buoyancy");
                 lbmhost::check(lbm_run_steps(h, n, done == 0), h, "lbm_run_steps");
                 lbmhost::check(lbm_store(h, nullptr, av_vels.data() + done, n), h, "lbm_store");
                 lbmhost::check(lbm_scalar_advance(h, n), h, "lbm_scalar_advance");

@@ -25,6 +25,9 @@
 * scalar_init, scalar_step, scalar_phi, scalar_apply_fixed, scalar_stats (+ ...3d)
                         -- the passive scalar of include/lbm_scalar_hip.h in fp32 numpy
                            (Engine.scalar_begin(), .scalar_advance(), .scalar(), .scalar_stats())
+* buoyancy_increments, buoyancy_kick (+ ...3d), rayleigh_number
+                        -- the Boussinesq kick of include/lbm_thermal_hip.h in fp32 numpy
+                           (Engine.scalar_buoyancy(), .run_thermal())
 
 Error behaviour follows the reference: loaders return None (std::nullopt)
 and print the reference's message on stderr.  One deliberate strengthening:
@@ -895,6 +898,88 @@ def scalar_stats(g, obst):
 
 
 scalar_stats3d = scalar_stats
+
+
+# ---- Boussinesq buoyancy (include/lbm_thermal_hip.h) ----
+#
+# The kick of the scalar on the flow in fp32 numpy, one ufunc per operation.  The
+# tables are read at call time: a test plants an error by replacing one.
+
+KICK_W = (np.float32(1) / np.float32(3), np.float32(1) / np.float32(12))      # 3 w_k of D2Q9: axis, diagonal speeds
+KICK_W3D = (np.float32(1) / np.float32(6), np.float32(1) / np.float32(12))    # of D3Q19
+# per opposite pair (plus speed, minus speed, terms of the increment): one term (component,) takes the axis
+# weight, two terms ((sign, component), (sign, component)) are diagonal-weight products added in that order
+KICK_PAIRS = ((1, 3, (0,)), (2, 4, (1,)), (5, 7, ((+1, 0), (+1, 1))), (6, 8, ((+1, 1), (-1, 0))))
+KICK_PAIRS3D = ((1, 2, (0,)), (3, 4, (1,)), (9, 14, (2,)),
+                (5, 6, ((+1, 0), (+1, 1))), (7, 8, ((+1, 0), (-1, 1))),
+                (10, 15, ((+1, 0), (+1, 2))), (11, 16, ((+1, 2), (-1, 0))),
+                (12, 17, ((+1, 1), (+1, 2))), (13, 18, ((+1, 2), (-1, 1))))
+
+
+def _buoyancy_increments(phi, density, s, phi_ref, w, pairs, q):
+    phi = np.asarray(phi, np.float32)
+    d = phi - np.float32(phi_ref)
+    j = [(np.float32(density) * np.float32(c)) * d for c in s]
+    a = [jc * w[0] for jc in j]
+    b = [jc * w[1] for jc in j]
+    inc = [None] * q
+    for plus, minus, terms in pairs:
+        if len(terms) == 1:
+            v = a[terms[0]]
+        else:
+            (s1, c1), (s2, c2) = terms
+            assert s1 > 0
+            v = (b[c1] + b[c2]) if s2 > 0 else (b[c1] - b[c2])
+        inc[plus], inc[minus] = v, -v
+    return inc
+
+
+def buoyancy_increments(phi, density, s, phi_ref=0.0):
+    """[None, d1 .. d8]: what lbm_scalar_buoyancy adds to speed k of a fluid cell whose scalar is phi
+    (float32 arrays of phi's shape; the rest speed gets nothing): 3 w_k density (c_k . s) (phi - phi_ref),
+    the increment of opp(k) the exact negative of that of k."""
+    if len(s) != 2:
+        raise ValueError("s = (sx, sy)")
+    return _buoyancy_increments(phi, density, s, phi_ref, KICK_W, KICK_PAIRS, 9)
+
+
+def buoyancy_increments3d(phi, density, s, phi_ref=0.0):
+    """[None, d1 .. d18] of lbm3d_scalar_buoyancy."""
+    if len(s) != 3:
+        raise ValueError("s = (sx, sy, sz)")
+    return _buoyancy_increments(phi, density, s, phi_ref, KICK_W3D, KICK_PAIRS3D, 19)
+
+
+def _buoyancy_kick(cells, g, obst, inc_of, s, q):
+    cells = np.array(cells, np.float32)
+    if cells.shape[-1] != q or np.asarray(g).shape[1:] != cells.shape[:-1]:
+        raise ValueError("cells AoS [...][q] and g planar [qs][...] of one domain")
+    if all(np.float32(c) == 0 for c in s):
+        return cells                     # no launch: every bit stays (x + 0 would turn a -0 into +0)
+    inc = inc_of(scalar_phi(g))
+    fluid = np.asarray(obst).reshape(cells.shape[:-1]) == 0
+    for k in range(1, q):
+        cells[..., k] = np.where(fluid, cells[..., k] + inc[k], cells[..., k])
+    return cells
+
+
+def buoyancy_kick(cells, g, obst, density, s, phi_ref=0.0) -> np.ndarray:
+    """A kicked copy of the AoS cells float32[ny][nx][9]: lbm_scalar_buoyancy(s, phi_ref) on a handle of
+    that density whose scalar populations are g (float32[5][ny][nx]).  Obstacle cells keep their bits."""
+    return _buoyancy_kick(cells, g, obst, lambda phi: buoyancy_increments(phi, density, s, phi_ref), s, 9)
+
+
+def buoyancy_kick3d(cells, g, obst, density, s, phi_ref=0.0) -> np.ndarray:
+    """lbm3d_scalar_buoyancy: cells float32[nz][ny][nx][19], g float32[7][nz][ny][nx]."""
+    return _buoyancy_kick(cells, g, obst, lambda phi: buoyancy_increments3d(phi, density, s, phi_ref), s, 19)
+
+
+def rayleigh_number(accel, dphi, height, omega, omega_s, dims: int = 2) -> float:
+    """Ra = accel dphi height^3 / (nu D): accel the buoyancy acceleration per unit of scalar and step,
+    dphi the scalar difference across `height` cells, nu = (1 / omega - 1/2) / 3 and D the scalar's
+    diffusivity (scalar_diffusivity)."""
+    nu = (1.0 / float(omega) - 0.5) / 3.0
+    return float(accel) * float(dphi) * float(height) ** 3 / (nu * scalar_diffusivity(omega_s, dims))
 
 
 def read_scalar_state(filename: str, nx: int, ny: int) -> np.ndarray:

@@ -123,6 +123,10 @@ EXPORTED_SCALAR = [
     "lbm3d_scalar_store", "lbm3d_scalar_stats", "lbm3d_scalar_end", "lbm3d_scalar_step_ref",
 ]
 SCALAR_MAX_PARTS = 16                     # LBM_SCALAR_MAX_PARTS
+# every symbol include/lbm_thermal_hip.h declares (Boussinesq buoyancy: the scalar's kick on the flow)
+EXPORTED_THERMAL = [
+    "lbm_scalar_buoyancy", "lbm_scalar_buoyancy_ref", "lbm3d_scalar_buoyancy", "lbm3d_scalar_buoyancy_ref",
+]
 SCALAR_Q, SCALAR_Q3D = 5, 7               # populations per cell of the scalar lattice
 Q3 = 19
 
@@ -361,6 +365,11 @@ def load_library() -> ctypes.CDLL:
         "lbm3d_scalar_stats": ([H, f64p, f32p, f32p], ctypes.c_int),
         "lbm3d_scalar_end": ([H], ctypes.c_int),
         "lbm3d_scalar_step_ref": ([i32, i32, i32, ctypes.c_float, f32p, f32p, f32p, u8p, f32p, f32p], ctypes.c_int),
+        # include/lbm_thermal_hip.h
+        "lbm_scalar_buoyancy": ([H] + [ctypes.c_float] * 3, ctypes.c_int),
+        "lbm3d_scalar_buoyancy": ([H] + [ctypes.c_float] * 4, ctypes.c_int),
+        "lbm_scalar_buoyancy_ref": ([i32, i32] + [ctypes.c_float] * 4 + [u8p, f32p, f32p], ctypes.c_int),
+        "lbm3d_scalar_buoyancy_ref": ([i32, i32, i32] + [ctypes.c_float] * 5 + [u8p, f32p, f32p], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -511,6 +520,31 @@ def scalar_step3d_ref(g, ux, uy, uz, obst, omega_s):
     return out
 
 
+def _buoyancy_ref(name, q, qs, cells, g, obst, density, s, phi_ref):
+    cells = np.array(cells, np.float32, order="C")
+    shape = cells.shape[:-1]
+    g = np.ascontiguousarray(g, np.float32)
+    obst = np.ascontiguousarray(obst, np.uint8)
+    if len(s) != len(shape) or cells.shape[-1] != q or g.shape != (qs,) + shape or obst.shape != shape:
+        raise ValueError("cells [..][q], g [qs][..] and obst [..] of one domain, s one component per axis")
+    rc = getattr(load_library(), name)(*shape[::-1], float(density), *[float(c) for c in s], float(phi_ref),
+                                       _ptr(obst), _ptr(g), _ptr(cells))
+    if rc != LBM_OK:
+        raise LbmError(rc, name + ": invalid argument")
+    return cells
+
+
+def scalar_buoyancy_ref(cells, g, obst, density, s, phi_ref=0.0):
+    """A kicked copy of the AoS cells float32[ny][nx][9]: lbm_scalar_buoyancy_ref -- the C++ per-cell
+    function of the kernel, compiled for the host (no GPU).  lio.buoyancy_kick restates it."""
+    return _buoyancy_ref("lbm_scalar_buoyancy_ref", 9, SCALAR_Q, cells, g, obst, density, s, phi_ref)
+
+
+def scalar_buoyancy3d_ref(cells, g, obst, density, s, phi_ref=0.0):
+    """lbm3d_scalar_buoyancy_ref: cells float32[nz][ny][nx][19].  lio.buoyancy_kick3d restates it."""
+    return _buoyancy_ref("lbm3d_scalar_buoyancy_ref", Q3, SCALAR_Q3D, cells, g, obst, density, s, phi_ref)
+
+
 def partition(nx: int, ny: int, parts: int, grid_rows: int = 0, grid_cols: int = 0):
     """Reference partition rule via the C ABI. Returns (rows, cols, [(x0,y0,w,h)...])."""
     L = load_library()
@@ -611,10 +645,11 @@ class _Handle:
         self._check(self._fn(name)(self._h, *args, *ptrs))
         return out
 
-    def _chunks(self, steps, every, accelerate_first, collect_av, after):
+    def _chunks(self, steps, every, accelerate_first, collect_av, after, before=None):
         """Advance `steps` steps in run_steps(every) chunks (the remainder last; accelerate_first on the
-        first chunk, D2Q9 only) and call after(n, done) behind each.  Returns the float32 concatenation
-        of the chunks' average velocities where collect_av asks for them (D2Q9 only), else an empty one."""
+        first chunk, D2Q9 only) and call after(n, done) behind each (and before(n) ahead of each).  Returns
+        the float32 concatenation of the chunks' average velocities where collect_av asks for them (D2Q9
+        only), else an empty one."""
         steps, every = int(steps), int(every)
         if steps < 0 or every < 1:
             raise ValueError("steps >= 0 and every >= 1")
@@ -624,6 +659,8 @@ class _Handle:
         av, done = [], 0
         while done < steps:
             n = min(every, steps - done)
+            if before is not None:
+                before(n)
             if two_d:
                 self.run_steps(n, accelerate_first and done == 0)
                 if collect_av:
@@ -1036,6 +1073,44 @@ class _Scalar:
         while done < steps:
             n = min(every, steps - done)
             self.run_scalar(n, stride, accelerate_first and done == 0)
+            done += n
+            out.append((done,) + self.scalar_stats())
+        return out
+
+    # Boussinesq buoyancy (include/lbm_thermal_hip.h)
+
+    def scalar_buoyancy(self, s, phi_ref: float = 0.0) -> None:
+        """Add the momentum density * s * (phi - phi_ref) to every fluid cell of the current lattice
+        (s = (sx, sy[, sz]): acceleration per unit of scalar times the flow steps it stands for):
+        lio.buoyancy_kick[3d] of store() and scalar(populations=True), bit for bit.  A run afterwards
+        continues as from load_cells of the kicked cells.  s = 0 launches nothing."""
+        s = [float(c) for c in s]
+        if len(s) != len(self._shape()):
+            raise ValueError(f"s has {len(self._shape())} components")
+        self._check(self._fn("scalar_buoyancy")(self._h, *s, float(phi_ref)))
+
+    def run_thermal(self, steps: int, accel, phi_ref: float = 0.0, stride: int = 1, accelerate_first: bool = False):
+        """Advance flow and scalar with the scalar driving the flow: per chunk of n <= stride steps
+        "scalar_buoyancy(n * accel, phi_ref), then run_steps(n), then scalar_advance(n)" (the remainder
+        last; scalar_begin first).  accel = (gx, gy[, gz]) is the acceleration per unit of scalar and
+        step.  stride = 1 is the exact first-order coupling; a larger stride applies the impulse of n
+        steps at once and freezes the velocity for n scalar steps, as run_scalar does.  Returns what
+        run_scalar returns."""
+        accel = [float(c) for c in accel]
+        return self._chunks(steps, stride, accelerate_first, True, lambda n, done: self.scalar_advance(n),
+                            before=lambda n: self.scalar_buoyancy([n * c for c in accel], phi_ref))
+
+    def thermal_history(self, steps: int, every: int, accel, phi_ref: float = 0.0, stride: int = 1,
+                        accelerate_first: bool = False):
+        """run_thermal(every, accel, phi_ref, stride) chunk after chunk (the remainder last),
+        scalar_stats() after each: a list of (step, total, min, max)."""
+        steps, every = int(steps), int(every)
+        if steps < 0 or every < 1:
+            raise ValueError("steps >= 0 and every >= 1")
+        out, done = [], 0
+        while done < steps:
+            n = min(every, steps - done)
+            self.run_thermal(n, accel, phi_ref, stride, accelerate_first and done == 0)
             done += n
             out.append((done,) + self.scalar_stats())
         return out
