@@ -69,8 +69,12 @@
  * LBM_SCALAR_MAX_PARTS local sub-domains, or on a handle that does not hold
  * the whole domain (begin: LBM_E_INVALID with a message); several scalar
  * steps per launch; caching the velocity across the sub-steps of a frozen
- * lattice; Dirichlet or flux wall models beyond the fixed list; time averages
- * of the scalar.
+ * lattice; Dirichlet or flux wall models beyond the fixed list; per-cell time
+ * accumulators of the scalar (time means at bin resolution, one-cell bins
+ * included, are sums of lbm_transport_hip.h's samples).
+ *
+ * How much scalar the flow carries -- face fluxes, u phi, Nusselt profiles --
+ * is lbm_transport_hip.h: binned sums of the scalar's transport terms.
  *
  * Feedback on the flow: lbm_thermal_hip.h (included below) adds the Boussinesq
  * buoyancy calls lbm_scalar_buoyancy / lbm3d_scalar_buoyancy, the one place

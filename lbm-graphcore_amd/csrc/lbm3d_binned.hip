@@ -73,15 +73,6 @@ hipError_t launch_binned_sums3d(const Bin3Args &a, hipStream_t s) {
 
 using namespace lbm;
 
-namespace {
-
-void check_bins(const lbm3d_params &p, int bw, int bh, int bd) {
-    if (bw < 1 || bw > p.nx || bh < 1 || bh > p.ny || bd < 1 || bd > p.nz)
-        throw lbm_failure(LBM_E_INVALID, "bin sizes must lie in 1..nx, 1..ny and 1..nz");
-}
-
-}  // namespace
-
 // The LBM3D_BIN_* sums of the current lattice into planar host arrays
 // double[nbz][nby][nbx] over the full bin grid (a NULL entry is neither staged
 // nor copied), slab after slab: a z bin that spans several slabs is summed in
@@ -89,7 +80,7 @@ void check_bins(const lbm3d_params &p, int bw, int bh, int bd) {
 void lbm3d_handle::store_binned(int bw, int bh, int bd, double *const *out) {
     using namespace lbm::binned;
     if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to take binned sums of");
-    check_bins(p, bw, bh, bd);
+    lbm::binned::check_bins(p.nx, p.ny, p.nz, bw, bh, bd);
     const int want = count_wanted(out, LBM3D_BIN_FIELDS);
     if (want == 0) return;
     const int nbx = LBM_BIN_COUNT(p.nx, bw), nby = LBM_BIN_COUNT(p.ny, bh), nbz = LBM_BIN_COUNT(p.nz, bd);
@@ -104,42 +95,18 @@ void lbm3d_handle::store_binned(int bw, int bh, int bd, double *const *out) {
         a.z = make_chunk_axis(s.z0, s.nzs, bd);
         a.nwx = (p.nx + BN3_WAVE_COLS - 1) / BN3_WAVE_COLS;
         a.nslots = a.nwx + a.x.nbl - 1;
-        const size_t part_n = (size_t)a.z.chunks() * p.ny * a.nslots;  // partials per field
-        const size_t bins_n = layer * a.z.a.nbl;                       // local bins
-        const DeviceStage stage(sizeof(double) * (part_n + bins_n) * want);
-        FoldArgs fa{};
-        fa.x = a.x;
-        fa.c = a.z;
-        fa.r = make_axis(0, p.ny, bh);
-        fa.wave_cols = BN3_WAVE_COLS;
-        fa.nslots = a.nslots;
-        fa.want = want;
-        double *bins = stage.as<double>() + part_n * want;
-        for (int i = 0, n = 0; i < LBM3D_BIN_FIELDS; ++i)
-            if (out[i]) {
-                a.part[i] = stage.as<double>() + part_n * n;
-                fa.part[n] = a.part[i];
-                fa.out[n] = bins + bins_n * n;
-                ++n;
-            }
+        const PartBins<LBM3D_BIN_FIELDS> pb(a.x, a.z, make_axis(0, p.ny, bh), (size_t)p.ny, BN3_WAVE_COLS, a.nslots, out);
+        std::copy(pb.part, pb.part + LBM3D_BIN_FIELDS, a.part);
         HIP_CHECK(launch_binned_sums3d(a, s.s_comp));
-        HIP_CHECK(launch_fold_bins(fa, s.s_comp));
-        HIP_CHECK(hipStreamSynchronize(s.s_comp));
-        std::vector<double> host(bins_n * want);
-        HIP_CHECK(hipMemcpy(host.data(), bins, sizeof(double) * host.size(), hipMemcpyDeviceToHost));
-        for (int i = 0, n = 0; i < LBM3D_BIN_FIELDS; ++i) {
-            if (!out[i]) continue;
-            const double *src = host.data() + bins_n * n++;
-            double *dst = out[i] + layer * a.z.a.b_lo;
-            for (size_t j = 0; j < bins_n; ++j) dst[j] += src[j];
-        }
+        HIP_CHECK(launch_fold_bins(pb.fa, s.s_comp));
+        pb.add_to(s.s_comp, out, nbx, nby);
     }
 }
 
 // Fluid cells per bin over the local slabs, from their obstacle maps (a copy
 // to the host, no launch).
 void lbm3d_handle::bin_fluid_cells(int bw, int bh, int bd, int64_t *count) {
-    check_bins(p, bw, bh, bd);
+    lbm::binned::check_bins(p.nx, p.ny, p.nz, bw, bh, bd);
     if (!count) return;
     const int nbx = LBM_BIN_COUNT(p.nx, bw), nby = LBM_BIN_COUNT(p.ny, bh), nbz = LBM_BIN_COUNT(p.nz, bd);
     std::fill(count, count + (size_t)nbx * nby * nbz, (int64_t)0);

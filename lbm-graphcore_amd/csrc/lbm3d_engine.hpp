@@ -13,6 +13,7 @@
 //   lbm3d_tracers.hip  Lagrangian tracers and point probes (host side; kernels in lbm_tracers.hpp);
 //   lbm3d_scalar.hip   passive scalar: a D3Q7 lattice beside the flow lattice (step kernel, host side;
 //                      shared parts in lbm_scalar.hpp);
+//   lbm3d_transport.hip binned transport sums of the scalar (kernel + host side; terms in lbm_transport.hpp);
 //   lbm3d_abi.hip      the extern "C" functions and the RCCL posting order.
 // The diagnostics units (fields to binned) share their host paths through
 // lbm_diag_host.hpp and their cell reads and block fold through lbm_quad.hpp.
@@ -300,4 +301,5 @@ struct lbm3d_handle {
     void scalar_stats(double *total, float *min, float *max);
     void scalar_end();
     void scalar_buoyancy(float sx, float sy, float sz, float phi_ref);  // include/lbm_thermal_hip.h
+    void scalar_store_binned(int bw, int bh, int bd, double *const *out);  // lbm3d_transport.hip; include/lbm_transport_hip.h
 };

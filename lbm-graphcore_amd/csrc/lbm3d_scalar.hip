@@ -52,8 +52,6 @@ struct Step3 : Box3View {
 
 namespace {
 
-__device__ __forceinline__ float pick(const float4 &v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
-
 // offset of cell (x, y, z) of the domain inside a scalar plane
 __device__ __forceinline__ long long goff(const Step3 &a, int x, int y, int z) {
     return ((long long)z * a.ny + y) * a.gsp + x;

@@ -178,15 +178,6 @@ hipError_t launch_binned_sums(const Bin2Args &a, hipStream_t s) {
 
 // ---- D2Q9 engine: host side ----
 
-namespace {
-
-void check_bins(const lbm_params &p, int bw, int bh) {
-    if (bw < 1 || bw > p.nx || bh < 1 || bh > p.ny)
-        throw lbm_failure(LBM_E_INVALID, "bin sizes must lie in 1..nx and 1..ny");
-}
-
-}  // namespace
-
 // The LBM_BIN_* sums of the current lattice into planar host arrays
 // double[nby][nbx] over the full bin grid.  A NULL entry is neither staged nor
 // copied.  Per sub-domain: first pass, second pass, the sub-domain's bin array
@@ -195,7 +186,7 @@ void check_bins(const lbm_params &p, int bw, int bh) {
 void lbm_handle::store_binned(int bw, int bh, double *const *out) {
     using namespace lbm::binned;
     if (!loaded) throw lbm_failure(LBM_E_STATE, "no lattice to take binned sums of");
-    check_bins(p, bw, bh);
+    lbm::binned::check_bins(p.nx, p.ny, 1, bw, bh, 1);
     const int want = count_wanted(out, LBM_BIN_FIELDS);
     if (want == 0) return;
     const int nbx = LBM_BIN_COUNT(p.nx, bw), nby = LBM_BIN_COUNT(p.ny, bh);
@@ -212,37 +203,11 @@ void lbm_handle::store_binned(int bw, int bh, double *const *out) {
         a.nslots = a.nwx + a.x.nbl - 1;
         if ((long long)a.y.chunks() * a.nwx > (1LL << 32))
             throw lbm_failure(LBM_E_INVALID, "sub-domain too large for binned sums");
-        const size_t part_n = (size_t)a.y.chunks() * a.nslots;  // partials per field
-        const size_t bins_n = (size_t)a.y.a.nbl * a.x.nbl;       // local bins
-        const DeviceStage stage(sizeof(double) * (part_n + bins_n) * want);
-        FoldArgs fa{};
-        fa.x = a.x;
-        fa.c = a.y;
-        fa.r = Axis{0, 1, 1, 0, 1};
-        fa.wave_cols = BN_WAVE_COLS;
-        fa.nslots = a.nslots;
-        fa.want = want;
-        double *bins = stage.as<double>() + part_n * want;
-        for (int i = 0, n = 0; i < LBM_BIN_FIELDS; ++i)
-            if (out[i]) {
-                a.part[i] = stage.as<double>() + part_n * n;
-                fa.part[n] = a.part[i];
-                fa.out[n] = bins + bins_n * n;
-                ++n;
-            }
+        const PartBins<LBM_BIN_FIELDS> pb(a.x, a.y, Axis{0, 1, 1, 0, 1}, 1, BN_WAVE_COLS, a.nslots, out);
+        std::copy(pb.part, pb.part + LBM_BIN_FIELDS, a.part);
         timed(s, s.s_comp, "binned_sums", [&] { HIP_CHECK(launch_binned_sums(a, s.s_comp)); });
-        timed(s, s.s_comp, "binned_sums fold", [&] { HIP_CHECK(launch_fold_bins(fa, s.s_comp)); });
-        HIP_CHECK(hipStreamSynchronize(s.s_comp));
-        std::vector<double> host(bins_n * want);
-        HIP_CHECK(hipMemcpy(host.data(), bins, sizeof(double) * host.size(), hipMemcpyDeviceToHost));
-        for (int i = 0, n = 0; i < LBM_BIN_FIELDS; ++i) {
-            if (!out[i]) continue;
-            const double *src = host.data() + bins_n * n++;
-            for (int by = 0; by < a.y.a.nbl; ++by) {
-                double *dst = out[i] + (size_t)(a.y.a.b_lo + by) * nbx + a.x.b_lo;
-                for (int bx = 0; bx < a.x.nbl; ++bx) dst[bx] += src[(size_t)by * a.x.nbl + bx];
-            }
-        }
+        timed(s, s.s_comp, "binned_sums fold", [&] { HIP_CHECK(launch_fold_bins(pb.fa, s.s_comp)); });
+        pb.add_to(s.s_comp, out, nbx, 1);
     }
     prof_collect();
 }
@@ -250,7 +215,7 @@ void lbm_handle::store_binned(int bw, int bh, double *const *out) {
 // Fluid cells per bin over the local sub-domains, from their obstacle maps (a
 // copy to the host, no launch).
 void lbm_handle::bin_fluid_cells(int bw, int bh, int64_t *count) {
-    check_bins(p, bw, bh);
+    lbm::binned::check_bins(p.nx, p.ny, 1, bw, bh, 1);
     if (!count) return;
     const int nbx = LBM_BIN_COUNT(p.nx, bw), nby = LBM_BIN_COUNT(p.ny, bh);
     std::fill(count, count + (size_t)nbx * nby, (int64_t)0);

@@ -1,7 +1,8 @@
 // lbm_binned.hpp -- what the binned-sum kernels of both engines share
 // (lbm_binned.hip, lbm3d_binned.hip; include/lbm_binned_hip.h): the geometry of
 // bins, waves and chunks, the per-cell term vectors, the segmented fold of a
-// wave's columns along x, and the argument block of the second pass.
+// wave's columns along x, the argument block of the second pass, and the host
+// side of a pass over one part (bin-size check, staging, copy back).
 //
 // A launch covers one sub-domain (D2Q9) or slab (D3Q19).  Bins tile the full
 // domain from global cell 0, so a sub-domain touches the bins b_lo .. b_lo + nbl
@@ -24,9 +25,11 @@
 
 #include <climits>
 #include <cstdint>
+#include <vector>
 
 #include "lbm3d_cell_macro.hpp"
 #include "lbm_cell_macro.hpp"
+#include "lbm_diag_host.hpp"
 
 namespace lbm {
 namespace binned {
@@ -207,6 +210,66 @@ struct FoldArgs {
 };
 
 hipError_t launch_fold_bins(const FoldArgs &a, hipStream_t s);  // lbm_binned.hip
+
+// ---- host side of a binned pass over one part (a sub-domain, a slab) ----
+// Shared by the flow's binned sums and the scalar transport sums (lbm_transport.hip, lbm3d_transport.hip).
+
+// bin sizes must lie in 1..n along each axis (an engine without z passes nz = bd = 1)
+inline void check_bins(int nx, int ny, int nz, int bw, int bh, int bd) {
+    if (bw < 1 || bw > nx || bh < 1 || bh > ny || bd < 1 || bd > nz)
+        throw lbm_failure(LBM_E_INVALID, "bin sizes must lie in 1..n along every axis");
+}
+
+// The staging of one part on the current device, held until it leaves scope: per requested field (out[f]
+// non-NULL, f < NF) the first pass's partials, part[f], and the part's local bin array.  The caller launches
+// its first pass over part[] and the second pass over fa, then calls add_to.
+template <int NF>
+class PartBins {
+    size_t part_n_, bins_n_;
+    int want_;
+    DeviceStage stage_;
+
+public:
+    double *part[NF] = {};  // in the header's field order; null where not requested
+    FoldArgs fa{};
+    // x, c, r: the axes of FoldArgs; rows: rows of a chunk that keep partials of their own (D2Q9: 1, D3Q19: ny)
+    PartBins(const Axis &x, const ChunkAxis &c, const Axis &r, size_t rows, int wave_cols, int nslots,
+             double *const *out)
+        : part_n_((size_t)c.chunks() * rows * nslots), bins_n_((size_t)c.a.nbl * r.nbl * x.nbl),
+          want_(count_wanted(out, NF)), stage_(sizeof(double) * (part_n_ + bins_n_) * want_) {
+        fa.x = x;
+        fa.c = c;
+        fa.r = r;
+        fa.wave_cols = wave_cols;
+        fa.nslots = nslots;
+        fa.want = want_;
+        double *bins = stage_.template as<double>() + part_n_ * want_;
+        for (int i = 0, n = 0; i < NF; ++i)
+            if (out[i]) {
+                part[i] = stage_.template as<double>() + part_n_ * n;
+                fa.part[n] = part[i];
+                fa.out[n] = bins + bins_n_ * n;
+                ++n;
+            }
+    }
+    // Once both passes are in st: waits for it, copies the part's bin arrays to the host and adds them into the
+    // bins they cover of out[f], double[..][nbr][nbx] over the full bin grid (nbr: the bins along the axis r,
+    // D2Q9: 1).  Called part after part, so a bin that spans several parts is summed in their order.
+    void add_to(hipStream_t st, double *const *out, int nbx, int nbr) const {
+        HIP_CHECK(hipStreamSynchronize(st));
+        std::vector<double> host(bins_n_ * want_);
+        HIP_CHECK(hipMemcpy(host.data(), fa.out[0], sizeof(double) * host.size(), hipMemcpyDeviceToHost));
+        const double *src = host.data();
+        for (int i = 0; i < NF; ++i) {
+            if (!out[i]) continue;
+            for (int bc = 0; bc < fa.c.a.nbl; ++bc)
+                for (int br = 0; br < fa.r.nbl; ++br) {
+                    double *dst = out[i] + ((size_t)(fa.c.a.b_lo + bc) * nbr + (fa.r.b_lo + br)) * nbx + fa.x.b_lo;
+                    for (int bx = 0; bx < fa.x.nbl; ++bx) dst[bx] += *src++;
+                }
+        }
+    }
+};
 
 }  // namespace binned
 }  // namespace lbm

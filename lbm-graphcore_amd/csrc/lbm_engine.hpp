@@ -20,6 +20,9 @@
 //   lbm_scalar.hip        passive scalar: a D2Q5 lattice beside the flow
 //                         lattice, advanced over the frozen flow (step kernel,
 //                         host side; shared parts in lbm_scalar.hpp);
+//   lbm_transport.hip     binned transport sums of the scalar: face fluxes,
+//                         u phi, phi (kernel over the binned sums' geometry,
+//                         host side; per-cell terms in lbm_transport.hpp);
 //   lbm_exchange.hip      partition rule, torus neighbours, halo destinations,
 //                         the posted exchange (RCCL or device copies);
 //   lbm_split.hip         work decomposition: boundary / interior split,
@@ -482,5 +485,6 @@ struct lbm_handle {
     void scalar_stats(double *total, float *min, float *max);
     void scalar_end();
     void scalar_buoyancy(float sx, float sy, float phi_ref);  // include/lbm_thermal_hip.h
+    void scalar_store_binned(int bw, int bh, double *const *out);  // lbm_transport.hip; include/lbm_transport_hip.h
     void destroy();
 };

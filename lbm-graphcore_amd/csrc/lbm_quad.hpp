@@ -51,6 +51,9 @@ __device__ __forceinline__ void quad_cell(const float4 (&v)[Q], int i, float (&c
     for (int k = 0; k < Q; ++k) c[k] = i == 0 ? v[k].x : i == 1 ? v[k].y : i == 2 ? v[k].z : v[k].w;
 }
 
+// value i (0..3) of a loaded quad
+__device__ __forceinline__ float pick(const float4 &v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
+
 // the Q populations of the single cell src + i
 template <int Q>
 __device__ __forceinline__ void load_cell(const float *src, long long speed_stride, int i, float (&c)[Q]) {

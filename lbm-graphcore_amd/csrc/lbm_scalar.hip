@@ -51,8 +51,6 @@ struct Step2 : LatticeView {
 
 namespace {
 
-__device__ __forceinline__ float pick(const float4 &v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
-
 // cell (x, y) of the sub-domain, every value loaded on its own
 __device__ __forceinline__ void step_one(const Step2 &a, int x, int y) {
     float c[Q];

@@ -5,7 +5,8 @@
 //              [--runs 5] [--kernel auto|resident|stream|step2|vec4|scalar|pipeline] [--spl S] [--out-dir DIR]
 //              [--tolerance] [--device-fields] [--forces] [--mean-every N] [--gradients] [--stress] [--binned BWxBH]
 //              [--tracers FILE [--trace-every N] [--trace-scheme euler|heun]]
-//              [--scalar FILE [--scalar-omega W] [--scalar-stride N] [--buoyancy GX,GY] [--scalar-ref R]]
+//              [--scalar FILE [--scalar-omega W] [--scalar-stride N] [--buoyancy GX,GY] [--scalar-ref R]
+//                             [--transport BWxBH]]
 //              [--json FILE]
 //
 // Flow (same program numbering as the reference):
@@ -60,6 +61,10 @@
 // then as many scalar steps over the frozen lattice, repeated -- and writes
 // scalar_state.dat after the run: `x y phi` per cell, x fastest, phi in %.9g
 // (lbm_scalar_hip.h).  GPU only.
+// --transport BWxBH (with --scalar) writes transport_state.dat after the run:
+// one line per bin of BW x BH cells, `bx by fluid` and then the six sums phi
+// phiphi uxphi uyphi fx fy in %.17g (lbm_transport_hip.h:
+// lbm_scalar_store_binned, lbm_bin_fluid_cells).  GPU only.
 // --buoyancy GX,GY (with --scalar) lets the scalar drive the flow: ahead of
 // every chunk of n <= --scalar-stride steps the momentum
 // density * n * (GX, GY) * (phi - R) is added to every fluid cell, R from
@@ -68,7 +73,7 @@
 // of --device ipumodel: exercises the multi-GPU halo path on one device).
 // --device cpu runs the same fused step on the host's cores (lbm_cpu.hpp:
 // OpenMP rows, bitwise equal to the GPU engine's default numerics); the
-// GPU-only options (-n, --tolerance, --kernel, --spl, --graph-steps, --device-fields, --mean-every, --scalar, --buoyancy) do not
+// GPU-only options (-n, --tolerance, --kernel, --spl, --graph-steps, --device-fields, --mean-every, --scalar, --buoyancy, --transport) do not
 // apply there and are refused with a message.
 #include <algorithm>
 #include <cstdio>
@@ -89,6 +94,7 @@
 #include "lbm_gradients_hip.h"
 #include "lbm_host.hpp"
 #include "lbm_scalar_hip.h"
+#include "lbm_transport_hip.h"
 #include "lbm_stress_hip.h"
 #include "lbm_tracers_hip.h"
 
@@ -137,6 +143,8 @@ void usage(const char *exe) {
               << "      --buoyancy arg   GX,GY: with --scalar, the scalar drives the flow -- ahead of every chunk of n steps\n"
               << "                       each fluid cell gains the momentum density * n * (GX, GY) * (phi - ref)\n"
               << "      --scalar-ref arg the ref of --buoyancy (default: 0)\n"
+              << "      --transport arg  BWxBH: with --scalar, also write transport_state.dat: per bin of BW x BH cells the\n"
+              << "                       fluid cells and the sums of phi, phi^2, ux phi, uy phi and the face fluxes FX, FY\n"
               << "      --out-dir arg    directory for av_vels.dat / final_state.dat (default: .)\n"
               << "      --graph-steps arg  replay the step loop as hipGraphs of 2*arg launches (0 = library default, <0 = off)\n"
               << "      --dump-partitioning arg  write the sub-domain decomposition as JSON\n"
@@ -254,6 +262,7 @@ int main(int argc, char *argv[]) {
     bool buoyant = false, scalarRefGiven = false;
     double buoyancyX = 0.0, buoyancyY = 0.0;
     float scalarRef = 0.f;
+    int transW = 0, transH = 0;
     std::vector<std::string> gpuOnly;  // GPU-only options given on the command line
     int spl = 0;
     int numGpus = 1, runs = 5, graphSteps = 0, meanEvery = 0, binW = 0, binH = 0;
@@ -352,6 +361,9 @@ int main(int argc, char *argv[]) {
             }
             buoyant = true;
             gpuOnly.push_back(a);
+        } else if (a == "--transport") {
+            if (!next(v) || sscanf(v.c_str(), "%dx%d", &transW, &transH) != 2) { usage(argv[0]); return EXIT_FAILURE; }
+            gpuOnly.push_back(a);
         } else if (a == "--scalar-ref") {
             if (!next(v)) { usage(argv[0]); return EXIT_FAILURE; }
             scalarRef = std::strtof(v.c_str(), nullptr);
@@ -411,6 +423,16 @@ int main(int argc, char *argv[]) {
     if ((buoyant || scalarRefGiven) && scalarFile.empty()) {
         std::cerr << "--buoyancy and --scalar-ref act on the scalar of --scalar FILE: give it too" << std::endl;
         return EXIT_FAILURE;
+    }
+    if (transW != 0 || transH != 0) {
+        if (scalarFile.empty()) {
+            std::cerr << "--transport sums the scalar of --scalar FILE: give it too" << std::endl;
+            return EXIT_FAILURE;
+        }
+        if (transW < 1 || transH < 1 || (size_t)transW > params->nx || (size_t)transH > params->ny) {
+            std::cerr << "--transport: bin sizes must lie in 1..nx and 1..ny" << std::endl;
+            return EXIT_FAILURE;
+        }
     }
     // --scalar: phi0 of every cell and the fixed list
     std::vector<float> scalarPhi, scalarFixedValue;
@@ -590,6 +612,8 @@ int main(int argc, char *argv[]) {
     std::vector<float> grads[LBM_GRAD_FIELDS];        // --gradients: gradient_state.dat's columns, planar
     std::vector<float> strain[LBM_STRESS_FIELDS];     // --stress: stress_state.dat's columns, planar
     lbmhost::BinnedSums binned;                       // --binned: binned_state.dat
+    std::vector<double> transport[LBM_SBIN_FIELDS];   // --transport: transport_state.dat's columns
+    std::vector<int64_t> transportFluid;
     lbmhost::timedStep("Running copy to host step", [&]() {
         if (deviceFields) {
             const size_t n = params->nx * params->ny;
@@ -645,6 +669,17 @@ int main(int argc, char *argv[]) {
                            "lbm_tracer_store");
             lbmhost::check(lbm_tracer_end(h), h, "lbm_tracer_end");
         }
+        if (transW > 0) {
+            const size_t bins = LBM_BIN_COUNT(params->nx, (size_t)transW) * LBM_BIN_COUNT(params->ny, (size_t)transH);
+            double *out[LBM_SBIN_FIELDS];
+            for (int f = 0; f < LBM_SBIN_FIELDS; ++f) {
+                transport[f].assign(bins, 0.0);
+                out[f] = transport[f].data();
+            }
+            transportFluid.assign(bins, 0);
+            lbmhost::check(lbm_scalar_store_binned(h, transW, transH, out), h, "lbm_scalar_store_binned");
+            lbmhost::check(lbm_bin_fluid_cells(h, transW, transH, transportFluid.data()), h, "lbm_bin_fluid_cells");
+        }
         if (!scalarFile.empty()) {
             lbmhost::check(lbm_scalar_store(h, scalarPhi.data(), nullptr), h, "lbm_scalar_store");
             lbmhost::check(lbm_scalar_end(h), h, "lbm_scalar_end");
@@ -681,6 +716,21 @@ int main(int argc, char *argv[]) {
                 for (size_t y = 0; y < params->ny; ++y)
                     for (size_t x = 0; x < params->nx; ++x)
                         fprintf(out, "%zu %zu %.9g\n", x, y, (double)scalarPhi[y * params->nx + x]);
+                fclose(out);
+            }
+        }
+        if (transW > 0) {
+            // transport_state.dat: `bx by fluid` and the six sums per bin, bx fastest; %.17g reads back to the same double
+            FILE *out = fopen((outDir + "/transport_state.dat").c_str(), "w");
+            if (!out) {
+                std::cerr << "Could not write transport_state.dat" << std::endl;
+            } else {
+                const size_t nbx = LBM_BIN_COUNT(params->nx, (size_t)transW);
+                for (size_t b = 0; b < transportFluid.size(); ++b) {
+                    fprintf(out, "%zu %zu %lld", b % nbx, b / nbx, (long long)transportFluid[b]);
+                    for (int f = 0; f < LBM_SBIN_FIELDS; ++f) fprintf(out, " %.17g", transport[f][b]);
+                    fprintf(out, "\n");
+                }
                 fclose(out);
             }
         }

@@ -982,6 +982,95 @@ def rayleigh_number(accel, dphi, height, omega, omega_s, dims: int = 2) -> float
     return float(accel) * float(dphi) * float(height) ** 3 / (nu * scalar_diffusivity(omega_s, dims))
 
 
+# ---- scalar transport sums (include/lbm_transport_hip.h) ----
+#
+# The face fluxes in fp32 numpy (one subtraction), the other terms in float64 as
+# the header widens them.  The tables are read at call time.
+
+# index order of LBM_SBIN_* / LBM3D_SBIN_*
+SBIN_FIELDS = ("phi", "phiphi", "uxphi", "uyphi", "fx", "fy")
+SBIN_FIELDS3D = ("phi", "phiphi", "uxphi", "uyphi", "uzphi", "fx", "fy", "fz")
+# per axis x, y[, z]: (speed that leaves the cell across the face, speed the neighbour sends back, array axis)
+SCALAR_FACES = ((1, 3, 1), (2, 4, 0))
+SCALAR_FACES3D = ((1, 2, 2), (3, 4, 1), (5, 6, 0))
+
+
+def _scalar_face_flux(g, faces):
+    g = np.asarray(g, np.float32)
+    return tuple(g[out] - np.roll(g[back], -1, axis=axis) for out, back, axis in faces)
+
+
+def scalar_face_flux(g):
+    """(FX, FY) float32[ny][nx]: what crosses the face on the high side of each cell in the next scalar
+    step, FX[y][x] = g1[y][x] - g3[y][x+1], FY[y][x] = g2[y][x] - g4[y+1][x], periodic.  The budget
+    phi' - phi = FX[x-1] - FX[x] + FY[y-1] - FY[y] holds up to fp32 rounding off the fixed list."""
+    return _scalar_face_flux(g, SCALAR_FACES)
+
+
+def scalar_face_flux3d(g):
+    """(FX, FY, FZ) float32[nz][ny][nx]: g1 - g2[x+1], g3 - g4[y+1], g5 - g6[z+1]."""
+    return _scalar_face_flux(g, SCALAR_FACES3D)
+
+
+def _scalar_terms(g, u, obst, faces, names):
+    phi = scalar_phi(g).astype(np.float64)
+    fluid = np.asarray(obst).reshape(phi.shape) == 0
+    zero = np.float64(0)
+    t = [np.where(fluid, phi, zero), np.where(fluid, phi * phi, zero)]
+    t += [np.where(fluid, np.asarray(c, np.float32).astype(np.float64) * phi, zero) for c in u]
+    t += [f.astype(np.float64) for f in _scalar_face_flux(g, faces)]
+    return dict(zip(names, t))
+
+
+def scalar_terms(g, ux, uy, obst):
+    """{name: float64[ny][nx]} of the per-cell terms the transport sums add, in SBIN_FIELDS order: phi,
+    phi^2 and u phi over the fluid cells (+0 on obstacles; phi the fp32 sum of the cell's populations,
+    ux, uy as Engine.fields() gives them, every product in float64, where it is exact), and the fp32 face
+    fluxes of every cell.  lbm_scalar_terms_ref gives the same bits."""
+    return _scalar_terms(g, (ux, uy), obst, SCALAR_FACES, SBIN_FIELDS)
+
+
+def scalar_terms3d(g, ux, uy, uz, obst):
+    """The same for D3Q7 beside D3Q19: {name: float64[nz][ny][nx]} in SBIN_FIELDS3D order."""
+    return _scalar_terms(g, (ux, uy, uz), obst, SCALAR_FACES3D, SBIN_FIELDS3D)
+
+
+def scalar_binned_sums(g, ux, uy, obst, bw: int, bh: int):
+    """The definition of lbm_scalar_store_binned restated: {name: float64[nby][nbx]} for the SBIN_FIELDS
+    -- per bin the exactly rounded sum (math.fsum) of scalar_terms(), from +0 -- and "fluid"."""
+    return _binned(scalar_terms(g, ux, uy, obst), obst, (bw, bh))
+
+
+def scalar_binned_sums3d(g, ux, uy, uz, obst, bw: int, bh: int, bd: int):
+    """lbm3d_scalar_store_binned: float64[nbz][nby][nbx] per SBIN_FIELDS3D name, and "fluid"."""
+    return _binned(scalar_terms3d(g, ux, uy, uz, obst), obst, (bw, bh, bd))
+
+
+def nusselt_number(flux_sum, area, diffusivity, dphi, height):
+    """The flux through a section of `area` faces (a plane sum of a face flux) over what pure conduction
+    carries across a layer `height` cells thick with the scalar difference dphi: area D dphi / height.
+    The fixed list overwrites with equilibrium, which puts the effective wall off the node (its place
+    depends on omega_s), so `height` is the caller's and results are best quoted against a conduction
+    run of the same set-up."""
+    return np.asarray(flux_sum, np.float64) / (float(area) * float(diffusivity) * float(dphi) / float(height))
+
+
+def read_transport_state(filename: str, nbx: int, nby: int):
+    """transport_state.dat (`bx by fluid` and the six SBIN_FIELDS sums in %.17g, bx fastest) back into
+    {name: float64[nby][nbx]} and "fluid": int64."""
+    out = {n: np.zeros((nby, nbx), np.float64) for n in SBIN_FIELDS}
+    out["fluid"] = np.zeros((nby, nbx), np.int64)
+    with open(filename, "r") as f:
+        for line in f:
+            t = line.split()
+            if t:
+                bx, by = int(t[0]), int(t[1])
+                out["fluid"][by, bx] = int(t[2])
+                for i, n in enumerate(SBIN_FIELDS):
+                    out[n][by, bx] = float(t[3 + i])
+    return out
+
+
 def read_scalar_state(filename: str, nx: int, ny: int) -> np.ndarray:
     """scalar_state.dat (`x y phi` per cell, phi in %.9g) -> float32[ny][nx]."""
     phi = np.zeros((ny, nx), np.float32)

@@ -128,6 +128,13 @@ EXPORTED_THERMAL = [
     "lbm_scalar_buoyancy", "lbm_scalar_buoyancy_ref", "lbm3d_scalar_buoyancy", "lbm3d_scalar_buoyancy_ref",
 ]
 SCALAR_Q, SCALAR_Q3D = 5, 7               # populations per cell of the scalar lattice
+# every symbol include/lbm_transport_hip.h declares (binned transport sums of the scalar; both engines)
+EXPORTED_TRANSPORT = [
+    "lbm_scalar_store_binned", "lbm3d_scalar_store_binned", "lbm_scalar_terms_ref", "lbm3d_scalar_terms_ref",
+]
+# index order of the output-pointer arrays (LBM_SBIN_* / LBM3D_SBIN_*)
+SBIN_FIELDS = ("phi", "phiphi", "uxphi", "uyphi", "fx", "fy")
+SBIN_FIELDS3D = ("phi", "phiphi", "uxphi", "uyphi", "uzphi", "fx", "fy", "fz")
 Q3 = 19
 
 
@@ -370,6 +377,11 @@ def load_library() -> ctypes.CDLL:
         "lbm3d_scalar_buoyancy": ([H] + [ctypes.c_float] * 4, ctypes.c_int),
         "lbm_scalar_buoyancy_ref": ([i32, i32] + [ctypes.c_float] * 4 + [u8p, f32p, f32p], ctypes.c_int),
         "lbm3d_scalar_buoyancy_ref": ([i32, i32, i32] + [ctypes.c_float] * 5 + [u8p, f32p, f32p], ctypes.c_int),
+        # include/lbm_transport_hip.h
+        "lbm_scalar_store_binned": ([H, i32, i32, f64pp], ctypes.c_int),
+        "lbm3d_scalar_store_binned": ([H, i32, i32, i32, f64pp], ctypes.c_int),
+        "lbm_scalar_terms_ref": ([i32, i32, f32p, f32p, u8p, f32p, f64p], ctypes.c_int),
+        "lbm3d_scalar_terms_ref": ([i32, i32, i32, f32p, f32p, f32p, u8p, f32p, f64p], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -543,6 +555,33 @@ def scalar_buoyancy_ref(cells, g, obst, density, s, phi_ref=0.0):
 def scalar_buoyancy3d_ref(cells, g, obst, density, s, phi_ref=0.0):
     """lbm3d_scalar_buoyancy_ref: cells float32[nz][ny][nx][19].  lio.buoyancy_kick3d restates it."""
     return _buoyancy_ref("lbm3d_scalar_buoyancy_ref", Q3, SCALAR_Q3D, cells, g, obst, density, s, phi_ref)
+
+
+def _terms_ref(name, names, qs, g, u, obst):
+    u, extent = _ref_fields(u, len(u))
+    shape = extent[::-1]
+    g = np.ascontiguousarray(g, np.float32)
+    obst = np.ascontiguousarray(obst, np.uint8)
+    if g.shape != (qs,) + shape or obst.shape != shape:
+        raise ValueError(f"g must be [{qs}][..] and obst [..] of the fields' shape")
+    terms = np.zeros((len(names),) + shape, np.float64)
+    rc = getattr(load_library(), name)(*extent, *[_ptr(c) for c in u], _ptr(obst), _ptr(g), _ptr(terms))
+    if rc != LBM_OK:
+        raise LbmError(rc, name + ": invalid argument")
+    return dict(zip(names, terms))
+
+
+def scalar_terms_ref(g, ux, uy, obst):
+    """{name: float64[ny][nx]} in SBIN_FIELDS order: lbm_scalar_terms_ref -- the per-cell terms of the
+    transport sums by the C++ function of the kernel, compiled for the host (no GPU).
+    lio.scalar_terms restates it."""
+    return _terms_ref("lbm_scalar_terms_ref", SBIN_FIELDS, SCALAR_Q, g, (ux, uy), obst)
+
+
+def scalar_terms3d_ref(g, ux, uy, uz, obst):
+    """lbm3d_scalar_terms_ref: {name: float64[nz][ny][nx]} in SBIN_FIELDS3D order.  lio.scalar_terms3d
+    restates it."""
+    return _terms_ref("lbm3d_scalar_terms_ref", SBIN_FIELDS3D, SCALAR_Q3D, g, (ux, uy, uz), obst)
 
 
 def partition(nx: int, ny: int, parts: int, grid_rows: int = 0, grid_cols: int = 0):
@@ -988,7 +1027,8 @@ class _Tracers:
 
 
 class _Scalar:
-    """Engine / Engine3D methods over include/lbm_scalar_hip.h; the class sets _SCALAR_Q."""
+    """Engine / Engine3D methods over include/lbm_scalar_hip.h, lbm_thermal_hip.h and lbm_transport_hip.h;
+    the class sets _SCALAR_Q and _SBIN_FIELDS."""
 
     def scalar_begin(self, phi0=None, omega_s=None, diffusivity=None) -> None:
         """Start (or restart) a passive scalar at phi0 (float32 array of the domain's shape; None:
@@ -1006,6 +1046,7 @@ class _Scalar:
             if phi0.shape != self._shape():
                 raise ValueError(f"phi0 must have the shape {self._shape()}")
         self._check(self._fn("scalar_begin")(self._h, float(omega_s), None if phi0 is None else _ptr(phi0)))
+        self._scalar_omega = float(np.float32(omega_s))           # the rate the device holds, for nusselt()
 
     def scalar_fix(self, x, y, *rest) -> None:
         """scalar_fix(x, y[, z], value): replace the fixed list by these distinct cells, which hold the
@@ -1116,6 +1157,72 @@ class _Scalar:
         return out
 
 
+    # binned transport sums (include/lbm_transport_hip.h)
+
+    def scalar_binned(self, *bins, which=None):
+        """{name: float64 array} of the sums over bins of bw x bh[ x bd] cells of the scalar's per-cell
+        transport terms -- "phi", "phiphi", "uxphi", "uyphi"[, "uzphi"] over the fluid cells and the face
+        fluxes "fx", "fy"[, "fz"] over all cells -- formed on the device from the current lattice and
+        scalar (lbm_scalar_store_binned), and "fluid": the fluid cells per bin.  Arrays are
+        [[nbz]][nby][nbx].  lio.scalar_binned_sums[3d] of fields() and scalar(populations=True) restates
+        them.  Default: every field.  Without a "u?phi" field the flow lattice is not read; with faces
+        only, just the planes those faces need."""
+        bins = tuple(int(b) for b in bins)
+        names = self._SBIN_FIELDS
+        out = self._store_fields("scalar_store_binned", names, _select(names, which, "transport fields"),
+                                 self._bin_shape(bins), np.float64, *bins)
+        out["fluid"] = self.bin_fluid_cells(*bins)
+        return out
+
+    def scalar_profile(self, axis: int, which=None):
+        """{name: float64[n_axis]}: the sums over every plane normal to `axis` (0 = x, 1 = y, 2 = z) of the
+        requested transport terms, and "fluid"."""
+        extent = self._shape()[::-1]                              # x first
+        if not 0 <= int(axis) < len(extent):
+            raise ValueError(f"axis is one of 0..{len(extent) - 1}")
+        bins = tuple(1 if c == int(axis) else n for c, n in enumerate(extent))
+        return {n: a.reshape(-1) for n, a in self.scalar_binned(*bins, which=which).items()}
+
+    def nusselt(self, axis: int, dphi: float, height: float):
+        """float64[n_axis]: per plane normal to `axis` the flux through the faces on its high side over
+        what pure conduction carries across `height` cells with the scalar difference dphi, area D dphi /
+        height (lio.nusselt_number).  Reads two scalar planes and nothing else.  In a steady state the
+        entries between a hot and a cold wall are equal."""
+        extent = self._shape()[::-1]
+        name = "f" + "xyz"[int(axis)]
+        flux = self.scalar_profile(axis, which=(name,))[name]
+        area = int(np.prod(extent)) // extent[int(axis)]
+        d = (1.0 / self._scalar_omega - 0.5) / (3.0 if len(extent) == 2 else 4.0)
+        return flux / (area * d * float(dphi) / float(height))
+
+    def transport_history(self, steps: int, every: int, *bins, which=None, accel=None, phi_ref: float = 0.0,
+                          stride: int = 1):
+        """run_thermal(every, accel, phi_ref, stride) chunk after chunk when `accel` is given, else
+        run_scalar(every, stride) (the remainder last), scalar_binned(*bins, which) after each.  Returns
+        {name: float64[samples, ...]} of the stacked samples, "step": the steps done at each sample, and
+        "fluid".  The operator is linear: sums of the samples over time are the binned time sums, so time
+        means of the scalar and its fluxes at bin resolution are means of these samples."""
+        steps, every = int(steps), int(every)
+        if steps < 0 or every < 1:
+            raise ValueError("steps >= 0 and every >= 1")
+        which = _select(self._SBIN_FIELDS, which, "transport fields")
+        samples, at, done = [], [], 0
+        while done < steps:
+            n = min(every, steps - done)
+            if accel is None:
+                self.run_scalar(n, stride)
+            else:
+                self.run_thermal(n, accel, phi_ref, stride)
+            done += n
+            samples.append(self.scalar_binned(*bins, which=which))
+            at.append(done)
+        shape = self._bin_shape(tuple(int(b) for b in bins))
+        out = {n: (np.stack([s[n] for s in samples]) if samples else np.zeros((0,) + shape)) for n in which}
+        out["step"] = np.asarray(at, np.int64)
+        out["fluid"] = self.bin_fluid_cells(*bins)
+        return out
+
+
 class Engine(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers, _Scalar):
     """One lbm_handle: the HIP counterpart of the reference's poplar::Engine."""
 
@@ -1126,6 +1233,7 @@ class Engine(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tra
     _BIN_FIELDS = BIN_FIELDS
     _TRACER_FIELDS = TRACER_FIELDS
     _SCALAR_Q = SCALAR_Q
+    _SBIN_FIELDS = SBIN_FIELDS
 
     def __init__(self, params, obstacles: np.ndarray, num_gpus: int = 1, *, parts: int | None = None,
                  grid=(0, 0), transport: int = TRANSPORT_LOCAL, rank: int = 0, world: int = 1,
@@ -1347,6 +1455,7 @@ class Engine3D(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _T
     _BIN_FIELDS = BIN_FIELDS3D
     _TRACER_FIELDS = TRACER_FIELDS3D
     _SCALAR_Q = SCALAR_Q3D
+    _SBIN_FIELDS = SBIN_FIELDS3D
 
     def __init__(self, params, obstacles: np.ndarray, *, parts: int = 1, transport: int = TRANSPORT_LOCAL,
                  rank: int = 0, world: int = 1, devices=None, unique_id: bytes | None = None, flags: int = 0):
