@@ -69,9 +69,13 @@
  * LBM_SCALAR_MAX_PARTS local sub-domains, or on a handle that does not hold
  * the whole domain (begin: LBM_E_INVALID with a message); several scalar
  * steps per launch; caching the velocity across the sub-steps of a frozen
- * lattice; Dirichlet or flux wall models beyond the fixed list; per-cell time
- * accumulators of the scalar (time means at bin resolution, one-cell bins
- * included, are sums of lbm_transport_hip.h's samples).
+ * lattice; per-cell time accumulators of the scalar (time means at bin
+ * resolution, one-cell bins included, are sums of lbm_transport_hip.h's
+ * samples).
+ *
+ * Walls that hold a value or a flux, and the scalar every body hands to the
+ * fluid, are lbm_scalar_walls_hip.h: a pass over the wall cells inside advance,
+ * after the step and before the fixed list.
  *
  * How much scalar the flow carries -- face fluxes, u phi, Nusselt profiles --
  * is lbm_transport_hip.h: binned sums of the scalar's transport terms.

@@ -14,6 +14,8 @@
 //   lbm3d_scalar.hip   passive scalar: a D3Q7 lattice beside the flow lattice (step kernel, host side;
 //                      shared parts in lbm_scalar.hpp);
 //   lbm3d_transport.hip binned transport sums of the scalar (kernel + host side; terms in lbm_transport.hpp);
+//   lbm3d_scalar_walls.hip wall models of the scalar and the per-body wall flux (host side; kernels in
+//                      lbm_scalar_walls.hpp);
 //   lbm3d_abi.hip      the extern "C" functions and the RCCL posting order.
 // The diagnostics units (fields to binned) share their host paths through
 // lbm_diag_host.hpp and their cell reads and block fold through lbm_quad.hpp.
@@ -302,4 +304,10 @@ struct lbm3d_handle {
     void scalar_end();
     void scalar_buoyancy(float sx, float sy, float sz, float phi_ref);  // include/lbm_thermal_hip.h
     void scalar_store_binned(int bw, int bh, int bd, double *const *out);  // lbm3d_transport.hip; include/lbm_transport_hip.h
+    // lbm3d_scalar_walls.hip (include/lbm_scalar_walls_hip.h)
+    std::vector<uint8_t> obst_host() const;
+    void scalar_set_walls(const int32_t *labels, int32_t nbodies, const int32_t *kind, const float *value);
+    void scalar_wall_flux(double *q, int64_t *links);
+    void scalar_body_flux(double *q, int64_t *links, int32_t nbodies);
+    void scalar_store_wall_flux(float *q);
 };

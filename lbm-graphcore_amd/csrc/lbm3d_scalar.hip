@@ -343,6 +343,8 @@ void lbm3d_handle::scalar_advance(int steps) {
         }
         t.cur ^= 1;
         ++t.steps;
+        // the wall models (include/lbm_scalar_walls_hip.h), before the fixed list
+        if (scalar::walls_listed(t)) HIP_CHECK(scalar::walls_pass3d(t, t.g[t.cur], st));
         scalar::apply_fixed<7>(t, t.g[t.cur], st, run_directly);
     }
     HIP_CHECK(hipStreamSynchronize(st));

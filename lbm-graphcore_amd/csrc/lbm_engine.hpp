@@ -23,6 +23,9 @@
 //   lbm_transport.hip     binned transport sums of the scalar: face fluxes,
 //                         u phi, phi (kernel over the binned sums' geometry,
 //                         host side; per-cell terms in lbm_transport.hpp);
+//   lbm_scalar_walls.hip  wall models of the scalar and the per-body wall
+//                         flux: a pass over the wall cells inside advance (host
+//                         side; kernels in lbm_scalar_walls.hpp);
 //   lbm_exchange.hip      partition rule, torus neighbours, halo destinations,
 //                         the posted exchange (RCCL or device copies);
 //   lbm_split.hip         work decomposition: boundary / interior split,
@@ -486,5 +489,11 @@ struct lbm_handle {
     void scalar_end();
     void scalar_buoyancy(float sx, float sy, float phi_ref);  // include/lbm_thermal_hip.h
     void scalar_store_binned(int bw, int bh, double *const *out);  // lbm_transport.hip; include/lbm_transport_hip.h
+    // scalar wall models and wall flux (lbm_scalar_walls.hip; include/lbm_scalar_walls_hip.h)
+    std::vector<uint8_t> obst_host() const;
+    void scalar_set_walls(const int32_t *labels, int32_t nbodies, const int32_t *kind, const float *value);
+    void scalar_wall_flux(double *q, int64_t *links);
+    void scalar_body_flux(double *q, int64_t *links, int32_t nbodies);
+    void scalar_store_wall_flux(float *q);
     void destroy();
 };

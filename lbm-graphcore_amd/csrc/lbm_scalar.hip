@@ -291,6 +291,8 @@ void lbm_handle::scalar_advance(int steps) {
         }
         t.cur ^= 1;
         ++t.steps;
+        if (scalar::walls_listed(t))  // the wall models (include/lbm_scalar_walls_hip.h), before the fixed list
+            timed(s0, s0.s_comp, "scalar_walls", [&] { HIP_CHECK(scalar::walls_pass2d(t, t.g[t.cur], s0.s_comp)); });
         scalar::apply_fixed<5>(t, t.g[t.cur], s0.s_comp,
                                [&](auto &&launch) { timed(s0, s0.s_comp, "scalar_fixed", launch); });
     }

@@ -160,6 +160,15 @@ struct Region {
     int x0, y0, z0, w, h, d;
 };
 
+struct Walls;                 // wall models and the wall list of a scalar (lbm_scalar_walls.hpp)
+void walls_free(Walls *w);    // lbm_scalar_walls.hip; NULL allowed, the device of the state current
+struct State;
+// The wall pass on set g, enqueued on st: D2Q5 (lbm_scalar_walls.hip) and D3Q7 (lbm3d_scalar_walls.hip).  Only
+// where walls_listed(s): a state without walls, or with no labelled wall cell, launches nothing.
+bool walls_listed(const State &s);
+hipError_t walls_pass2d(const State &s, float *g, hipStream_t st);
+hipError_t walls_pass3d(const State &s, float *g, hipStream_t st);
+
 struct State {
     int dev = 0, q = 0;
     Grid grid{};
@@ -171,6 +180,7 @@ struct State {
     long long nfixed = 0;
     long long *fix_cell = nullptr;  // offset of each fixed cell inside a speed plane
     float *fix_value = nullptr;
+    Walls *walls = nullptr;  // set by *_scalar_set_walls (include/lbm_scalar_walls_hip.h); NULL: none
     size_t set_floats() const { return (size_t)q * (size_t)grid.plane; }
 };
 
@@ -244,6 +254,7 @@ inline void release(State *s) {
         (void)hipFree(s->g[0]);
         (void)hipFree(s->fix_cell);
         (void)hipFree(s->fix_value);
+        walls_free(s->walls);
     }
     delete s;
 }

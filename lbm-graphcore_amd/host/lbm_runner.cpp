@@ -6,7 +6,7 @@
 //              [--tolerance] [--device-fields] [--forces] [--mean-every N] [--gradients] [--stress] [--binned BWxBH]
 //              [--tracers FILE [--trace-every N] [--trace-scheme euler|heun]]
 //              [--scalar FILE [--scalar-omega W] [--scalar-stride N] [--buoyancy GX,GY] [--scalar-ref R]
-//                             [--transport BWxBH]]
+//                             [--transport BWxBH] [--scalar-walls FILE2]]
 //              [--json FILE]
 //
 // Flow (same program numbering as the reference):
@@ -65,6 +65,13 @@
 // one line per bin of BW x BH cells, `bx by fluid` and then the six sums phi
 // phiphi uxphi uyphi fx fy in %.17g (lbm_transport_hip.h:
 // lbm_scalar_store_binned, lbm_bin_fluid_cells).  GPU only.
+// --scalar-walls FILE2 (with --scalar) reads one body per line, `body kind
+// value` (kind 0 adiabatic, 1 fixed wall value, 2 fixed flux per link and
+// step; bodies numbered as for --forces, unlisted bodies adiabatic), gives the
+// bodies those wall models for the run and writes wall_flux.dat after it:
+// `body kind value q links` per body, value in %.9g, q -- the scalar the body
+// handed to the fluid in the last step -- in %.17g (lbm_scalar_walls_hip.h:
+// lbm_scalar_set_walls, lbm_scalar_body_flux).  GPU only.
 // --buoyancy GX,GY (with --scalar) lets the scalar drive the flow: ahead of
 // every chunk of n <= --scalar-stride steps the momentum
 // density * n * (GX, GY) * (phi - R) is added to every fluid cell, R from
@@ -73,7 +80,7 @@
 // of --device ipumodel: exercises the multi-GPU halo path on one device).
 // --device cpu runs the same fused step on the host's cores (lbm_cpu.hpp:
 // OpenMP rows, bitwise equal to the GPU engine's default numerics); the
-// GPU-only options (-n, --tolerance, --kernel, --spl, --graph-steps, --device-fields, --mean-every, --scalar, --buoyancy, --transport) do not
+// GPU-only options (-n, --tolerance, --kernel, --spl, --graph-steps, --device-fields, --mean-every, --scalar, --buoyancy, --transport, --scalar-walls) do not
 // apply there and are refused with a message.
 #include <algorithm>
 #include <cstdio>
@@ -94,6 +101,7 @@
 #include "lbm_gradients_hip.h"
 #include "lbm_host.hpp"
 #include "lbm_scalar_hip.h"
+#include "lbm_scalar_walls_hip.h"
 #include "lbm_transport_hip.h"
 #include "lbm_stress_hip.h"
 #include "lbm_tracers_hip.h"
@@ -143,6 +151,9 @@ void usage(const char *exe) {
               << "      --buoyancy arg   GX,GY: with --scalar, the scalar drives the flow -- ahead of every chunk of n steps\n"
               << "                       each fluid cell gains the momentum density * n * (GX, GY) * (phi - ref)\n"
               << "      --scalar-ref arg the ref of --buoyancy (default: 0)\n"
+              << "      --scalar-walls arg   file of `body kind value` lines: with --scalar, wall models of the scalar per\n"
+              << "                       obstacle body (kind 0 adiabatic, 1 wall value, 2 flux per link and step; bodies as\n"
+              << "                       for --forces), and also write wall_flux.dat: body kind value q links\n"
               << "      --transport arg  BWxBH: with --scalar, also write transport_state.dat: per bin of BW x BH cells the\n"
               << "                       fluid cells and the sums of phi, phi^2, ux phi, uy phi and the face fluxes FX, FY\n"
               << "      --out-dir arg    directory for av_vels.dat / final_state.dat (default: .)\n"
@@ -256,7 +267,7 @@ int main(int argc, char *argv[]) {
     std::string paramsFile, obstaclesFile, device = "gpu", exeFile, kernel = "auto", outDir = ".", dumpFile, jsonFile;
     std::string tracersFile, traceSchemeName = "heun";
     int traceEvery = 10;
-    std::string scalarFile;
+    std::string scalarFile, wallsFile;
     float scalarOmega = 1.0f;
     int scalarStride = 1;
     bool buoyant = false, scalarRefGiven = false;
@@ -364,6 +375,9 @@ int main(int argc, char *argv[]) {
         } else if (a == "--transport") {
             if (!next(v) || sscanf(v.c_str(), "%dx%d", &transW, &transH) != 2) { usage(argv[0]); return EXIT_FAILURE; }
             gpuOnly.push_back(a);
+        } else if (a == "--scalar-walls") {
+            if (!next(wallsFile)) { usage(argv[0]); return EXIT_FAILURE; }
+            gpuOnly.push_back(a);
         } else if (a == "--scalar-ref") {
             if (!next(v)) { usage(argv[0]); return EXIT_FAILURE; }
             scalarRef = std::strtof(v.c_str(), nullptr);
@@ -432,6 +446,38 @@ int main(int argc, char *argv[]) {
         if (transW < 1 || transH < 1 || (size_t)transW > params->nx || (size_t)transH > params->ny) {
             std::cerr << "--transport: bin sizes must lie in 1..nx and 1..ny" << std::endl;
             return EXIT_FAILURE;
+        }
+    }
+    // --scalar-walls: the bodies of --forces with a kind and a value each
+    std::vector<int32_t> wallLabels, wallKind;
+    std::vector<float> wallValue;
+    if (!wallsFile.empty()) {
+        if (scalarFile.empty()) {
+            std::cerr << "--scalar-walls sets the walls of the scalar of --scalar FILE: give it too" << std::endl;
+            return EXIT_FAILURE;
+        }
+        const int32_t nbodies = lbmhost::labelBodies(*obstacles, wallLabels);
+        wallKind.assign(nbodies, LBM_SCALAR_WALL_ADIABATIC);
+        wallValue.assign(nbodies, 0.f);
+        std::ifstream f(wallsFile);
+        if (!f) {
+            std::cerr << "Could not read the scalar walls from " << wallsFile << std::endl;
+            return EXIT_FAILURE;
+        }
+        std::string line;
+        while (std::getline(f, line)) {
+            if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+            long body = -1;
+            int kind = -1;
+            float value = 0.f;
+            if (sscanf(line.c_str(), "%ld %d %f", &body, &kind, &value) != 3 || body < 0 || body >= nbodies ||
+                kind < LBM_SCALAR_WALL_ADIABATIC || kind > LBM_SCALAR_WALL_FLUX || !std::isfinite(value)) {
+                std::cerr << "Malformed --scalar-walls line (body kind value; body in 0.." << nbodies - 1
+                          << ", kind in 0..2, value finite): " << line << std::endl;
+                return EXIT_FAILURE;
+            }
+            wallKind[body] = kind;
+            wallValue[body] = value;
         }
     }
     // --scalar: phi0 of every cell and the fixed list
@@ -590,6 +636,10 @@ int main(int argc, char *argv[]) {
             lbmhost::check(lbm_scalar_set_fixed(h, (int64_t)scalarFixedX.size(), scalarFixedX.data(),
                                                 scalarFixedY.data(), scalarFixedValue.data()),
                            h, "lbm_scalar_set_fixed");
+            if (!wallKind.empty())
+                lbmhost::check(lbm_scalar_set_walls(h, wallLabels.data(), (int32_t)wallKind.size(), wallKind.data(),
+                                                    wallValue.data()),
+                               h, "lbm_scalar_set_walls");
             for (int done = 0; done < (int)params->maxIters;) {
                 const int n = std::min(scalarStride, (int)params->maxIters - done);
                 if (buoyant)  // the impulse of the chunk's n steps at once
@@ -614,6 +664,8 @@ int main(int argc, char *argv[]) {
     lbmhost::BinnedSums binned;                       // --binned: binned_state.dat
     std::vector<double> transport[LBM_SBIN_FIELDS];   // --transport: transport_state.dat's columns
     std::vector<int64_t> transportFluid;
+    std::vector<double> wallFlux(wallKind.size(), 0.0);       // --scalar-walls: wall_flux.dat's columns
+    std::vector<int64_t> wallLinks(wallKind.size(), 0);
     lbmhost::timedStep("Running copy to host step", [&]() {
         if (deviceFields) {
             const size_t n = params->nx * params->ny;
@@ -680,6 +732,9 @@ int main(int argc, char *argv[]) {
             lbmhost::check(lbm_scalar_store_binned(h, transW, transH, out), h, "lbm_scalar_store_binned");
             lbmhost::check(lbm_bin_fluid_cells(h, transW, transH, transportFluid.data()), h, "lbm_bin_fluid_cells");
         }
+        if (!wallKind.empty())
+            lbmhost::check(lbm_scalar_body_flux(h, wallFlux.data(), wallLinks.data(), (int32_t)wallKind.size()), h,
+                           "lbm_scalar_body_flux");
         if (!scalarFile.empty()) {
             lbmhost::check(lbm_scalar_store(h, scalarPhi.data(), nullptr), h, "lbm_scalar_store");
             lbmhost::check(lbm_scalar_end(h), h, "lbm_scalar_end");
@@ -731,6 +786,18 @@ int main(int argc, char *argv[]) {
                     for (int f = 0; f < LBM_SBIN_FIELDS; ++f) fprintf(out, " %.17g", transport[f][b]);
                     fprintf(out, "\n");
                 }
+                fclose(out);
+            }
+        }
+        if (!wallsFile.empty()) {
+            // wall_flux.dat: `body kind value q links` per body; %.9g and %.17g read back to the same float and double
+            FILE *out = fopen((outDir + "/wall_flux.dat").c_str(), "w");
+            if (!out) {
+                std::cerr << "Could not write wall_flux.dat" << std::endl;
+            } else {
+                for (size_t b = 0; b < wallKind.size(); ++b)
+                    fprintf(out, "%zu %d %.9g %.17g %lld\n", b, (int)wallKind[b], (double)wallValue[b], wallFlux[b],
+                            (long long)wallLinks[b]);
                 fclose(out);
             }
         }

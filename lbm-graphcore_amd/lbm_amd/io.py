@@ -1071,6 +1071,126 @@ def read_transport_state(filename: str, nbx: int, nby: int):
     return out
 
 
+# ---- scalar wall models and the wall flux (include/lbm_scalar_walls_hip.h) ----
+#
+# The header's definition in fp32 numpy, one ufunc per operation.  The tables and
+# the two one-line functions are read at call time: a test plants an error by
+# replacing one.
+
+WALL_ADIABATIC, WALL_VALUE, WALL_FLUX = 0, 1, 2
+# vectors (x, y[, z]) of the scalar speeds, in the speed order of lbm_scalar_hip.h
+SCALAR_E = ((0, 0), (1, 0), (0, 1), (-1, 0), (0, -1))
+SCALAR_E3D = ((0, 0, 0), (1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1))
+
+
+def scalar_wall_links(obstacles) -> np.ndarray:
+    """uint32[ny][nx]: bit k-1 set iff the cell is blocked and its neighbour along scalar speed k
+    (E, N, W, S; periodic) is not -- link k of include/lbm_scalar_walls_hip.h.  Non-zero = wall cell."""
+    return _links(np.asarray(obstacles).reshape(np.shape(obstacles)[-2:]), SCALAR_E)
+
+
+def scalar_wall_links3d(obstacles) -> np.ndarray:
+    """uint32[nz][ny][nx] link masks of the D3Q7 lattice (bits 0..5: +x -x +y -y +z -z)."""
+    return _links(obstacles, SCALAR_E3D)
+
+
+def _wall_reflect(m, gk):
+    """g_k of a fixed-value wall: d - g_k with d = m + m (anti-bounce-back)."""
+    d = m + m
+    return d - gk
+
+
+def _wall_handed(m, gk):
+    """What a fixed-value link hands to the fluid: (g_k - m) * 2."""
+    return (gk - m) * np.float32(2)
+
+
+def _wall_table(links, obst, labels, kinds, values):
+    """Per cell: (kind, value) of its body where it is a wall cell of a labelled body, else (0, +0)."""
+    kinds = np.asarray(kinds, np.int32).reshape(-1)
+    values = np.asarray(values, np.float32).reshape(-1)
+    lab = np.asarray(labels).reshape(links.shape)
+    nb = kinds.size
+    if nb < 1 or values.size != nb or ((kinds < 0) | (kinds > 2)).any() or not np.isfinite(values).all():
+        raise ValueError("one kind in 0..2 and one finite value per body, at least one body")
+    if (lab[np.asarray(obst).reshape(links.shape) != 0] >= nb).any():
+        raise ValueError("labels of blocked cells must be < nbodies (negative: no body)")
+    on = (links != 0) & (lab >= 0)
+    idx = np.where(on, lab, 0)
+    return np.where(on, kinds[idx], 0), np.where(on, values[idx], np.float32(0)).astype(np.float32)
+
+
+def _scalar_apply_walls(g, obst, labels, kinds, values, links, w):
+    g = np.array(g, np.float32)
+    kind, v = _wall_table(links, obst, labels, kinds, values)
+    m = v * w[1]
+    for k in range(1, g.shape[0]):
+        link = ((links >> np.uint32(k - 1)) & np.uint32(1)) != 0
+        gk = g[k].copy()
+        g[k] = np.where(link & (kind == WALL_VALUE), _wall_reflect(m, gk),
+                        np.where(link & (kind == WALL_FLUX), gk + v, gk))
+    return g
+
+
+def scalar_apply_walls(g, obst, labels, kinds, values) -> np.ndarray:
+    """A copy of g float32[5][ny][nx] after the wall pass of lbm_scalar_advance: on every set link of
+    a wall cell of body b (labels int[ny][nx], negative = no body) g_k <- 2 v w1 - g_k for kinds[b] = 1
+    (fixed value v = values[b]) or g_k <- g_k + v for kinds[b] = 2 (fixed flux); everything else keeps
+    its bits.  lbm_scalar_walls_ref gives the same bits."""
+    return _scalar_apply_walls(g, obst, labels, kinds, values, scalar_wall_links(obst), SCALAR_W)
+
+
+def scalar_apply_walls3d(g, obst, labels, kinds, values) -> np.ndarray:
+    """The D3Q7 twin: g float32[7][nz][ny][nx]."""
+    return _scalar_apply_walls(g, obst, labels, kinds, values, scalar_wall_links3d(obst), SCALAR_W3D)
+
+
+def _scalar_wall_flux_cells(g, obst, labels, kinds, values, links, w):
+    g = np.asarray(g, np.float32)
+    kind, v = _wall_table(links, obst, labels, kinds, values)
+    m = v * w[1]
+    zero = np.float32(0)
+    t = [None]
+    for k in range(1, g.shape[0]):
+        link = ((links >> np.uint32(k - 1)) & np.uint32(1)) != 0
+        t.append(np.where(link & (kind == WALL_VALUE), _wall_handed(m, g[k]),
+                          np.where(link & (kind == WALL_FLUX), v, zero)).astype(np.float32))
+    return _seq(t, *range(1, g.shape[0])).astype(np.float32)
+
+
+def scalar_wall_flux_cells(g, obst, labels, kinds, values) -> np.ndarray:
+    """float32[ny][nx]: per wall cell the scalar its links handed to the fluid in the step (and pass)
+    that produced g, exactly as include/lbm_scalar_walls_hip.h defines it; +0 elsewhere."""
+    return _scalar_wall_flux_cells(g, obst, labels, kinds, values, scalar_wall_links(obst), SCALAR_W)
+
+
+def scalar_wall_flux_cells3d(g, obst, labels, kinds, values) -> np.ndarray:
+    return _scalar_wall_flux_cells(g, obst, labels, kinds, values, scalar_wall_links3d(obst), SCALAR_W3D)
+
+
+def scalar_wall_flux(g, obst, labels, kinds, values):
+    """((q, links), (q[nbodies], links[nbodies])): the fp64 sums of scalar_wall_flux_cells over all
+    wall cells with the links of all wall cells, and the per-body sums."""
+    links = scalar_wall_links(obst)
+    return _totals(links, (_scalar_wall_flux_cells(g, obst, labels, kinds, values, links, SCALAR_W),), labels,
+                   np.asarray(kinds).size)
+
+
+def scalar_wall_flux3d(g, obst, labels, kinds, values):
+    links = scalar_wall_links3d(obst)
+    return _totals(links, (_scalar_wall_flux_cells(g, obst, labels, kinds, values, links, SCALAR_W3D),), labels,
+                   np.asarray(kinds).size)
+
+
+def read_wall_flux(filename: str):
+    """wall_flux.dat (`body kind value q links` per line) -> (kind int32[n], value float32[n],
+    q float64[n], links int64[n]) in body order."""
+    rows = [line.split() for line in open(filename, "r") if line.split()]
+    rows.sort(key=lambda t: int(t[0]))
+    return (np.array([int(t[1]) for t in rows], np.int32), np.array([np.float32(t[2]) for t in rows], np.float32),
+            np.array([float(t[3]) for t in rows], np.float64), np.array([int(t[4]) for t in rows], np.int64))
+
+
 def read_scalar_state(filename: str, nx: int, ny: int) -> np.ndarray:
     """scalar_state.dat (`x y phi` per cell, phi in %.9g) -> float32[ny][nx]."""
     phi = np.zeros((ny, nx), np.float32)

@@ -135,6 +135,15 @@ EXPORTED_TRANSPORT = [
 # index order of the output-pointer arrays (LBM_SBIN_* / LBM3D_SBIN_*)
 SBIN_FIELDS = ("phi", "phiphi", "uxphi", "uyphi", "fx", "fy")
 SBIN_FIELDS3D = ("phi", "phiphi", "uxphi", "uyphi", "uzphi", "fx", "fy", "fz")
+# every symbol include/lbm_scalar_walls_hip.h declares (scalar wall models and the per-body wall flux; both engines)
+EXPORTED_WALLS = [
+    "lbm_scalar_set_walls", "lbm_scalar_wall_flux", "lbm_scalar_body_flux", "lbm_scalar_store_wall_flux",
+    "lbm_scalar_walls_ref",
+    "lbm3d_scalar_set_walls", "lbm3d_scalar_wall_flux", "lbm3d_scalar_body_flux", "lbm3d_scalar_store_wall_flux",
+    "lbm3d_scalar_walls_ref",
+]
+SCALAR_WALL_ADIABATIC, SCALAR_WALL_VALUE, SCALAR_WALL_FLUX = 0, 1, 2   # LBM_SCALAR_WALL_*
+SCALAR_WALL_KINDS = {"adiabatic": SCALAR_WALL_ADIABATIC, "value": SCALAR_WALL_VALUE, "flux": SCALAR_WALL_FLUX}
 Q3 = 19
 
 
@@ -382,6 +391,17 @@ def load_library() -> ctypes.CDLL:
         "lbm3d_scalar_store_binned": ([H, i32, i32, i32, f64pp], ctypes.c_int),
         "lbm_scalar_terms_ref": ([i32, i32, f32p, f32p, u8p, f32p, f64p], ctypes.c_int),
         "lbm3d_scalar_terms_ref": ([i32, i32, i32, f32p, f32p, f32p, u8p, f32p, f64p], ctypes.c_int),
+        # include/lbm_scalar_walls_hip.h
+        "lbm_scalar_set_walls": ([H, i32p, i32, i32p, f32p], ctypes.c_int),
+        "lbm_scalar_wall_flux": ([H, f64p, i64p], ctypes.c_int),
+        "lbm_scalar_body_flux": ([H, f64p, i64p, i32], ctypes.c_int),
+        "lbm_scalar_store_wall_flux": ([H, f32p], ctypes.c_int),
+        "lbm_scalar_walls_ref": ([i32, i32, u8p, i32p, i32, i32p, f32p, f32p, f32p], ctypes.c_int),
+        "lbm3d_scalar_set_walls": ([H, i32p, i32, i32p, f32p], ctypes.c_int),
+        "lbm3d_scalar_wall_flux": ([H, f64p, i64p], ctypes.c_int),
+        "lbm3d_scalar_body_flux": ([H, f64p, i64p, i32], ctypes.c_int),
+        "lbm3d_scalar_store_wall_flux": ([H, f32p], ctypes.c_int),
+        "lbm3d_scalar_walls_ref": ([i32, i32, i32, u8p, i32p, i32, i32p, f32p, f32p, f32p], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -582,6 +602,44 @@ def scalar_terms3d_ref(g, ux, uy, uz, obst):
     """lbm3d_scalar_terms_ref: {name: float64[nz][ny][nx]} in SBIN_FIELDS3D order.  lio.scalar_terms3d
     restates it."""
     return _terms_ref("lbm3d_scalar_terms_ref", SBIN_FIELDS3D, SCALAR_Q3D, g, (ux, uy, uz), obst)
+
+
+def _wall_table(kinds, values):
+    """(kind int32[n], value float32[n]); a kind may be a name of SCALAR_WALL_KINDS."""
+    kinds = [SCALAR_WALL_KINDS[k] if isinstance(k, str) else int(k) for k in np.asarray(kinds, object).reshape(-1)]
+    kind = np.ascontiguousarray(kinds, np.int32)
+    value = np.ascontiguousarray(values, np.float32).reshape(-1)
+    if kind.size != value.size:
+        raise ValueError("one kind and one value per body")
+    return kind, value
+
+
+def _walls_ref(name, qs, g, obst, labels, kinds, values, flux):
+    g = np.array(g, np.float32, order="C")
+    shape = g.shape[1:]
+    obst = np.ascontiguousarray(obst, np.uint8)
+    labels = np.ascontiguousarray(labels, np.int32)
+    kind, value = _wall_table(kinds, values)
+    if g.shape[0] != qs or len(shape) != (2 if qs == SCALAR_Q else 3) or obst.shape != shape or labels.shape != shape:
+        raise ValueError(f"g must be [{qs}][..], obst and labels [..] of one domain")
+    q = np.zeros(shape, np.float32) if flux else None
+    rc = getattr(load_library(), name)(*shape[::-1], _ptr(obst), _ptr(labels), kind.size, _ptr(kind), _ptr(value),
+                                       _ptr(g), None if q is None else _ptr(q))
+    if rc != LBM_OK:
+        raise LbmError(rc, name + ": invalid argument")
+    return (g, q) if flux else g
+
+
+def scalar_walls_ref(g, obst, labels, kinds, values, flux=False):
+    """A copy of g float32[5][ny][nx] after the wall pass, and with `flux` also the per-cell wall flux of
+    the result: lbm_scalar_walls_ref -- the C++ per-cell functions of the kernels, compiled for the host
+    (no GPU).  lio.scalar_apply_walls and lio.scalar_wall_flux_cells restate it."""
+    return _walls_ref("lbm_scalar_walls_ref", SCALAR_Q, g, obst, labels, kinds, values, flux)
+
+
+def scalar_walls3d_ref(g, obst, labels, kinds, values, flux=False):
+    """lbm3d_scalar_walls_ref: g float32[7][nz][ny][nx].  lio.scalar_apply_walls3d restates it."""
+    return _walls_ref("lbm3d_scalar_walls_ref", SCALAR_Q3D, g, obst, labels, kinds, values, flux)
 
 
 def partition(nx: int, ny: int, parts: int, grid_rows: int = 0, grid_cols: int = 0):
@@ -1047,6 +1105,7 @@ class _Scalar:
                 raise ValueError(f"phi0 must have the shape {self._shape()}")
         self._check(self._fn("scalar_begin")(self._h, float(omega_s), None if phi0 is None else _ptr(phi0)))
         self._scalar_omega = float(np.float32(omega_s))           # the rate the device holds, for nusselt()
+        self._scalar_nbodies = 0                                  # begin drops the walls
 
     def scalar_fix(self, x, y, *rest) -> None:
         """scalar_fix(x, y[, z], value): replace the fixed list by these distinct cells, which hold the
@@ -1093,6 +1152,7 @@ class _Scalar:
     def scalar_end(self) -> None:
         """Free the scalar lattice (close() frees it too)."""
         self._check(self._fn("scalar_end")(self._h))
+        self._scalar_nbodies = 0
 
     def run_scalar(self, steps: int, stride: int = 1, accelerate_first: bool = False):
         """Advance flow and scalar together: repeat "run_steps(stride), then scalar_advance(stride)"
@@ -1221,6 +1281,77 @@ class _Scalar:
         out["step"] = np.asarray(at, np.int64)
         out["fluid"] = self.bin_fluid_cells(*bins)
         return out
+
+
+    # wall models and the per-body wall flux (include/lbm_scalar_walls_hip.h)
+
+    _scalar_nbodies = 0
+
+    def scalar_walls(self, labels, kinds=None, values=None) -> None:
+        """Give the bodies of `labels` (int32 map of the full domain, e.g. lio.label_bodies; negative =
+        no body, adiabatic) a wall model each: kinds[b] in ("adiabatic", "value", "flux") or 0..2 and
+        values[b], the wall value or the scalar added per link and step.  From the next scalar_advance
+        on every step is lio.scalar_step[3d], then lio.scalar_apply_walls[3d], then the fixed list, bit
+        for bit.  scalar_walls(None, 0) clears the walls; scalar_begin and scalar_end drop them."""
+        if labels is None:
+            self._check(self._fn("scalar_set_walls")(self._h, None, 0, None, None))
+            self._scalar_nbodies = 0
+            return
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.size != int(np.prod(self._shape())):
+            raise ValueError("labels must cover the full domain")
+        kind, value = _wall_table(kinds, values)
+        self._check(self._fn("scalar_set_walls")(self._h, _ptr(lab), kind.size, _ptr(kind), _ptr(value)))
+        self._scalar_nbodies = int(kind.size)
+
+    def scalar_wall_values(self, kinds, values) -> None:
+        """Replace the per-body table alone (as many bodies as scalar_walls set): a wall value that
+        changes in time.  The wall list is not rebuilt."""
+        kind, value = _wall_table(kinds, values)
+        self._check(self._fn("scalar_set_walls")(self._h, None, kind.size, _ptr(kind), _ptr(value)))
+
+    def scalar_wall_flux(self):
+        """(q, links): the scalar all wall cells handed to the fluid in the last scalar step (the fp64 sum
+        of the fp32 per-cell values, folded in a fixed order) and the links of all wall cells."""
+        q, links = ctypes.c_double(), ctypes.c_int64()
+        self._check(self._fn("scalar_wall_flux")(self._h, ctypes.byref(q), ctypes.byref(links)))
+        return q.value, links.value
+
+    def scalar_body_flux(self):
+        """(q[nbodies], links[nbodies]) of the bodies scalar_walls set, summed on the device."""
+        n = self._scalar_nbodies
+        q, links = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.int64)
+        self._check(self._fn("scalar_body_flux")(self._h, _ptr(q), _ptr(links), n))
+        return q[:n], links[:n]
+
+    def scalar_wall_flux_field(self):
+        """float32 map of the per-cell wall flux, +0 off the walls -- lio.scalar_wall_flux_cells[3d] of
+        scalar(populations=True), bit for bit."""
+        q = np.zeros(self._shape(), np.float32)
+        self._check(self._fn("scalar_store_wall_flux")(self._h, _ptr(q)))
+        return q
+
+    def wall_flux_history(self, steps: int, every: int, accel=None, phi_ref: float = 0.0, stride: int = 1):
+        """run_thermal(every, accel, phi_ref, stride) chunk after chunk when `accel` is given, else
+        run_scalar(every, stride) (the remainder last), scalar_body_flux() after each.  Returns
+        {"step": int64[samples], "q": float64[samples, nbodies], "links": int64[nbodies]}."""
+        steps, every = int(steps), int(every)
+        if steps < 0 or every < 1:
+            raise ValueError("steps >= 0 and every >= 1")
+        samples, at, done = [], [], 0
+        links = np.zeros(self._scalar_nbodies, np.int64)
+        while done < steps:
+            n = min(every, steps - done)
+            if accel is None:
+                self.run_scalar(n, stride)
+            else:
+                self.run_thermal(n, accel, phi_ref, stride)
+            done += n
+            q, links = self.scalar_body_flux()
+            samples.append(q)
+            at.append(done)
+        return {"step": np.asarray(at, np.int64),
+                "q": np.stack(samples) if samples else np.zeros((0, self._scalar_nbodies)), "links": links}
 
 
 class Engine(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers, _Scalar):
