@@ -125,7 +125,12 @@ int lbm_scalar_store(lbm_handle *h, float *phi, float *g);
 
 /* total: the fp64 sum of every cell's fp32 phi, folded in a fixed order (two
  * calls give identical bits); min, max: over the fluid cells (+Inf, -Inf when
- * there is none).  NULL entries are skipped; all NULL launches nothing. */
+ * there is none).  NULL entries are skipped; all NULL launches nothing.
+ * Non-finite scalars: the extremes are folded with fmaxf, which drops a NaN
+ * operand, so a NaN phi of a fluid cell is left out of min and max (all fluid
+ * cells NaN: +Inf, -Inf, as with none) while +-Inf take part as values; the
+ * sum is plain IEEE addition, so total is NaN as soon as any cell, fluid or
+ * blocked, holds a NaN phi or cells hold infinities of both signs. */
 int lbm_scalar_stats(lbm_handle *h, double *total, float *min, float *max);
 
 /* Frees the state (lbm_destroy frees it too).  LBM_OK on a handle without one. */

@@ -889,12 +889,19 @@ def scalar_apply_fixed3d(g, x, y, z, value) -> np.ndarray:
 def scalar_stats(g, obst):
     """(total, min, max) of lbm_scalar_stats: the float64 sum of every cell's float32 phi (math.fsum:
     the exact sum, which the device's fold approaches within its bound) and the extremes over the
-    fluid cells (+inf, -inf when there is none).  Either lattice."""
+    fluid cells (+inf, -inf when there is none).  Either lattice.  Non-finite scalars as the header
+    states them: a NaN phi of a fluid cell is left out of the extremes (fmaxf drops it), infinities
+    take part; the total is the IEEE sum, NaN with a NaN anywhere or with infinities of both signs."""
     import math
     phi = scalar_phi(g)
     fluid = phi[np.asarray(obst) == 0]
-    total = math.fsum(phi.astype(np.float64).ravel().tolist())
-    return total, np.float32(fluid.min(initial=np.inf)), np.float32(fluid.max(initial=-np.inf))
+    terms = phi.astype(np.float64).ravel()
+    if np.isfinite(terms).all():
+        total = math.fsum(terms.tolist())
+    else:
+        with np.errstate(invalid="ignore"):
+            total = float(np.sum(terms))     # NaN, or the one infinity the non-finite terms share
+    return total, np.float32(np.fmin.reduce(fluid, initial=np.inf)), np.float32(np.fmax.reduce(fluid, initial=-np.inf))
 
 
 scalar_stats3d = scalar_stats
