@@ -17,7 +17,7 @@ struct Cell3Macro {
 };
 
 // the momentum (rho u_x, rho u_y, rho u_z): the numerators cell3_macro divides by rho
-__device__ __forceinline__ void cell3_momentum(const float (&s)[19], float &jx, float &jy, float &jz) {
+__host__ __device__ __forceinline__ void cell3_momentum(const float (&s)[19], float &jx, float &jy, float &jz) {
     jx = (s[1] + s[5] + s[7] + s[10] + s[16]) - (s[2] + s[6] + s[8] + s[11] + s[15]);
     jy = (s[3] + s[5] + s[8] + s[12] + s[18]) - (s[4] + s[6] + s[7] + s[13] + s[17]);
     jz = (s[9] + s[10] + s[11] + s[12] + s[13]) - (s[14] + s[15] + s[16] + s[17] + s[18]);

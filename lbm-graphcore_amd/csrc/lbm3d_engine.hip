@@ -694,6 +694,7 @@ void lbm3d_handle::destroy() {
     avg_end();
     tracer_end();
     scalar_end();
+    forcing_clear();
     grad_release();
     stress_release();
     for (auto &s : slabs) {

@@ -16,6 +16,8 @@
 //   lbm3d_transport.hip binned transport sums of the scalar (kernel + host side; terms in lbm_transport.hpp);
 //   lbm3d_scalar_walls.hip wall models of the scalar and the per-body wall flux (host side; kernels in
 //                      lbm_scalar_walls.hpp);
+//   lbm3d_forcing.hip  forcing zones: body force, drag and velocity target on boxes of cells (kernel, host
+//                      side; shared parts in lbm_forcing.hpp);
 //   lbm3d_abi.hip      the extern "C" functions and the RCCL posting order.
 // The diagnostics units (fields to binned) share their host paths through
 // lbm_diag_host.hpp and their cell reads and block fold through lbm_quad.hpp.
@@ -45,6 +47,9 @@ struct State;  // point set of a handle that keeps tracers (lbm_tracers.hpp)
 }
 namespace scalar {
 struct State;  // scalar lattice of a handle that carries a passive scalar (lbm_scalar.hpp)
+}
+namespace forcing {
+struct State;  // zones of a handle that set a forcing zone (lbm_forcing.hpp)
 }
 namespace grad {
 struct Grad3Args;  // lbm_gradients.hpp
@@ -310,4 +315,12 @@ struct lbm3d_handle {
     void scalar_wall_flux(double *q, int64_t *links);
     void scalar_body_flux(double *q, int64_t *links, int32_t nbodies);
     void scalar_store_wall_flux(float *q);
+    void need_whole_domain(const char *what) const;  // lbm3d_scalar.hip: the restrictions of scalar_begin
+    // lbm3d_forcing.hip (include/lbm_forcing_hip.h)
+    lbm::forcing::State *forcing = nullptr;  // built at the first zone set
+    void forcing_set_zone(int zone, int x0, int y0, int z0, int w, int h, int d, const float *const *coef,
+                          const float *konst);
+    void forcing_clear();
+    void forcing_zones(int32_t *n_set, uint32_t *mask) const;
+    void forcing_apply(float steps, double *impulse);
 };

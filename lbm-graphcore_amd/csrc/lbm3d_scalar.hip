@@ -261,9 +261,7 @@ __global__ __launch_bounds__(S3X *S3Y) void scalar_buoyancy3d(Kick3 a) {
     }
 }
 
-namespace {
-
-// the grid of both kernels over a whole-slab view
+// the grid of both kernels over a whole-slab view (and of the forcing zones over a box: lbm_scalar.hpp)
 dim3 slab_grid(const Box3View &a) {
     const int cpl = a.quad ? 4 : 1;
     const long long lanes = ((long long)a.bx + cpl - 1) / cpl;
@@ -274,7 +272,8 @@ dim3 slab_grid(const Box3View &a) {
     return dim3((unsigned)gx, (unsigned)gy, (unsigned)gz);
 }
 
-}  // namespace
+int slab_lanes_x() { return S3X; }
+int slab_rows() { return S3Y; }
 
 }  // namespace scalar
 }  // namespace lbm
@@ -294,19 +293,26 @@ const auto run_directly = [](auto &&launch) { launch(); };  // no profile classe
 
 // ---- D3Q19 engine: host side ----
 
-void lbm3d_handle::scalar_begin(float omega_s, const float *phi0) {
+// What a feature that keeps one global array beside the lattice asks of the handle (the scalar; the forcing zones
+// of lbm3d_forcing.hip): one device, the whole domain here, at most 16 local slabs, no RCCL world > 1.
+void lbm3d_handle::need_whole_domain(const char *what) const {
+    const std::string w(what);
     if (transport == LBM_TRANSPORT_RCCL && world > 1)
-        throw lbm_failure(LBM_E_INVALID, "scalars on RCCL handles of more than one rank are not built");
+        throw lbm_failure(LBM_E_INVALID, w + " on RCCL handles of more than one rank are not built");
     if ((int)slabs.size() > scalar::MAX_PARTS)
-        throw lbm_failure(LBM_E_INVALID, "scalars on more than 16 local slabs are not built");
+        throw lbm_failure(LBM_E_INVALID, w + " on more than 16 local slabs are not built");
     int planes = 0;
     for (const auto &s : slabs) {
         if (s.dev != slabs[0].dev)
-            throw lbm_failure(LBM_E_INVALID, "scalars on slabs of more than one device are not built");
+            throw lbm_failure(LBM_E_INVALID, w + " on slabs of more than one device are not built");
         planes += s.nzs;
     }
     if (slabs.empty() || planes != p.nz)
-        throw lbm_failure(LBM_E_INVALID, "scalars need every slab of the domain on this handle");
+        throw lbm_failure(LBM_E_INVALID, w + " need every slab of the domain on this handle");
+}
+
+void lbm3d_handle::scalar_begin(float omega_s, const float *phi0) {
+    need_whole_domain("scalars");
     scalar::check_omega(omega_s);
     sync_all();
     scalar::begin(scalars, slabs[0].dev, 7, p.nx, p.ny, p.nz, omega_s, phi0);

@@ -17,7 +17,7 @@ struct CellMacro {
 };
 
 // the momentum (rho u_x, rho u_y): the numerators cell_macro divides by rho
-__device__ __forceinline__ void cell_momentum(const float (&c)[9], float &jx, float &jy) {
+__host__ __device__ __forceinline__ void cell_momentum(const float (&c)[9], float &jx, float &jy) {
     jx = c[1] + c[5] + c[8] - (c[3] + c[6] + c[7]);
     jy = c[2] + c[5] + c[6] - (c[4] + c[7] + c[8]);
 }

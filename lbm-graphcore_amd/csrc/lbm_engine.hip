@@ -930,6 +930,7 @@ void lbm_handle::destroy() {
     avg_end();
     tracer_end();
     scalar_end();
+    forcing_clear();
     grad_release();
     stress_release();
     for (auto &s : subs) {

@@ -26,6 +26,10 @@
 //   lbm_scalar_walls.hip  wall models of the scalar and the per-body wall
 //                         flux: a pass over the wall cells inside advance (host
 //                         side; kernels in lbm_scalar_walls.hpp);
+//   lbm_forcing.hip       forcing zones: body force, drag and velocity
+//                         target on boxes of cells, an impulse on the current
+//                         lattice (kernel, host side; shared parts in
+//                         lbm_forcing.hpp);
 //   lbm_exchange.hip      partition rule, torus neighbours, halo destinations,
 //                         the posted exchange (RCCL or device copies);
 //   lbm_split.hip         work decomposition: boundary / interior split,
@@ -127,6 +131,9 @@ struct State;  // point set of a handle that keeps tracers (lbm_tracers.hpp)
 }
 namespace scalar {
 struct State;  // scalar lattice of a handle that carries a passive scalar (lbm_scalar.hpp)
+}
+namespace forcing {
+struct State;  // zones of a handle that set a forcing zone (lbm_forcing.hpp)
 }
 namespace stress {
 struct State;       // near-wall class maps of a handle that asked for strain statistics (lbm_stress.hip)
@@ -495,5 +502,12 @@ struct lbm_handle {
     void scalar_wall_flux(double *q, int64_t *links);
     void scalar_body_flux(double *q, int64_t *links, int32_t nbodies);
     void scalar_store_wall_flux(float *q);
+    void need_whole_domain(const char *what) const;  // lbm_scalar.hip: the restrictions of scalar_begin
+    // forcing zones (lbm_forcing.hip; include/lbm_forcing_hip.h)
+    lbm::forcing::State *forcing = nullptr;  // built at the first zone set
+    void forcing_set_zone(int zone, int x0, int y0, int w, int h, const float *const *coef, const float *konst);
+    void forcing_clear();
+    void forcing_zones(int32_t *n_set, uint32_t *mask) const;
+    void forcing_apply(float steps, double *impulse);
     void destroy();
 };

@@ -233,19 +233,26 @@ scalar::Region region_of(const Sub &s) { return scalar::Region{s.obst, s.rect.x0
 
 // ---- D2Q9 engine: host side ----
 
-void lbm_handle::scalar_begin(float omega_s, const float *phi0) {
+// What a feature that keeps one global array beside the lattice asks of the handle (the scalar; the forcing zones
+// of lbm_forcing.hip): one device, the whole domain here, at most 16 local parts, no RCCL world > 1.
+void lbm_handle::need_whole_domain(const char *what) const {
+    const std::string w(what);
     if (transport == LBM_TRANSPORT_RCCL && world > 1)
-        throw lbm_failure(LBM_E_INVALID, "scalars on RCCL handles of more than one rank are not built");
+        throw lbm_failure(LBM_E_INVALID, w + " on RCCL handles of more than one rank are not built");
     if ((int)subs.size() > scalar::MAX_PARTS)
-        throw lbm_failure(LBM_E_INVALID, "scalars on more than 16 local sub-domains are not built");
+        throw lbm_failure(LBM_E_INVALID, w + " on more than 16 local sub-domains are not built");
     long long cells = 0;
     for (const auto &s : subs) {
         if (s.dev != subs[0].dev)
-            throw lbm_failure(LBM_E_INVALID, "scalars on sub-domains of more than one device are not built");
+            throw lbm_failure(LBM_E_INVALID, w + " on sub-domains of more than one device are not built");
         cells += (long long)s.w * s.h;
     }
     if (subs.empty() || cells != (long long)p.nx * p.ny)
-        throw lbm_failure(LBM_E_INVALID, "scalars need every sub-domain of the domain on this handle");
+        throw lbm_failure(LBM_E_INVALID, w + " need every sub-domain of the domain on this handle");
+}
+
+void lbm_handle::scalar_begin(float omega_s, const float *phi0) {
+    need_whole_domain("scalars");
     scalar::check_omega(omega_s);
     sync_all();
     scalar::begin(scalars, subs[0].dev, 5, p.nx, p.ny, 1, omega_s, phi0);

@@ -112,9 +112,8 @@ LBM_HD float cell_phi(const float (&g)[Q]) {
 }
 
 // D2Q9: E/W, N/S, NE/SW, NW/SE
-LBM_HD void kick2_inc(float phi, float phi_ref, float kx, float ky, float (&inc)[KICK2_PAIRS]) {
-    const float d = phi - phi_ref;
-    const float jx = kx * d, jy = ky * d;
+// the pair increments of the momentum (jx, jy); the forcing zones (lbm_forcing.hpp) form theirs through it too
+LBM_HD void kick2_pairs(float jx, float jy, float (&inc)[KICK2_PAIRS]) {
     inc[0] = jx * (1.f / 3.f);
     inc[1] = jy * (1.f / 3.f);
     const float bx = jx * (1.f / 12.f), by = jy * (1.f / 12.f);
@@ -122,10 +121,13 @@ LBM_HD void kick2_inc(float phi, float phi_ref, float kx, float ky, float (&inc)
     inc[3] = by - bx;
 }
 
-// D3Q19: +-x, +-y, +-z, then the six diagonal pairs in the order of kick3_plus
-LBM_HD void kick3_inc(float phi, float phi_ref, float kx, float ky, float kz, float (&inc)[KICK3_PAIRS]) {
+LBM_HD void kick2_inc(float phi, float phi_ref, float kx, float ky, float (&inc)[KICK2_PAIRS]) {
     const float d = phi - phi_ref;
-    const float jx = kx * d, jy = ky * d, jz = kz * d;
+    kick2_pairs(kx * d, ky * d, inc);
+}
+
+// D3Q19: +-x, +-y, +-z, then the six diagonal pairs in the order of kick3_plus
+LBM_HD void kick3_pairs(float jx, float jy, float jz, float (&inc)[KICK3_PAIRS]) {
     inc[0] = jx * (1.f / 6.f);
     inc[1] = jy * (1.f / 6.f);
     inc[2] = jz * (1.f / 6.f);
@@ -136,6 +138,11 @@ LBM_HD void kick3_inc(float phi, float phi_ref, float kx, float ky, float kz, fl
     inc[6] = bz - bx;
     inc[7] = by + bz;
     inc[8] = bz - by;
+}
+
+LBM_HD void kick3_inc(float phi, float phi_ref, float kx, float ky, float kz, float (&inc)[KICK3_PAIRS]) {
+    const float d = phi - phi_ref;
+    kick3_pairs(kx * d, ky * d, kz * d, inc);
 }
 
 // One pair of one cell.  A select of the loaded value, not an added zero: an obstacle cell keeps its bits
@@ -428,6 +435,13 @@ inline bool kick_args_ok(int nx, int ny, int nz, std::initializer_list<float> nu
         if (!p) return false;
     return true;
 }
+
+// The launch shape of the D3Q19 kernels that walk a box of a slab a row of lanes at a time (lbm3d_scalar.hip; the
+// forcing zones of lbm3d_forcing.hip launch on it too): the grid over the view's box, the lanes of a block along x
+// and its rows.
+dim3 slab_grid(const Box3View &a);
+int slab_lanes_x();
+int slab_rows();
 
 #undef LBM_HD
 

@@ -38,7 +38,8 @@ struct Box3View {
 
 // The writable counterparts, for the one kind of kernel that changes the
 // current lattice in place between runs (the buoyancy kick of lbm_scalar.hip /
-// lbm3d_scalar.hip): `e` is the same origin as `o`, writable, and such a kernel
+// lbm3d_scalar.hip, the forcing zones of lbm_forcing.hip / lbm3d_forcing.hip):
+// `e` is the same origin as `o`, writable, and such a kernel
 // reads and writes through it alone.  Owned cells only: the ghost cells are
 // left to the engine (lbm_handle::lattice_edit, lbm3d_handle::slab_edit).
 struct LatticeEdit : LatticeView {

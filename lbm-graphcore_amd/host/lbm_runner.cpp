@@ -5,6 +5,7 @@
 //              [--runs 5] [--kernel auto|resident|stream|step2|vec4|scalar|pipeline] [--spl S] [--out-dir DIR]
 //              [--tolerance] [--device-fields] [--forces] [--mean-every N] [--gradients] [--stress] [--binned BWxBH]
 //              [--tracers FILE [--trace-every N] [--trace-scheme euler|heun]]
+//              [--forcing FILE [--forcing-stride N]]
 //              [--scalar FILE [--scalar-omega W] [--scalar-stride N] [--buoyancy GX,GY] [--scalar-ref R]
 //                             [--transport BWxBH] [--scalar-walls FILE2]]
 //              [--json FILE]
@@ -76,11 +77,18 @@
 // every chunk of n <= --scalar-stride steps the momentum
 // density * n * (GX, GY) * (phi - R) is added to every fluid cell, R from
 // --scalar-ref (default 0) (lbm_thermal_hip.h: lbm_scalar_buoyancy).
+// --forcing FILE reads uniform forcing zones, one per line,
+// `zone x0 y0 w h lam utx uty fx fy` (lines that start with # are skipped), and
+// runs the first run through the forced loop: ahead of every chunk of
+// n <= --forcing-stride (default 1) steps every zone is applied as the impulse
+// of n steps (lbm_forcing_hip.h: lbm_forcing_apply).  It writes forcing.dat
+// after the run: `zone ix iy` per zone, the momentum the zone added summed
+// over the run, in %.17g.  The timed re-runs are free runs.  GPU only.
 // --device loopback places all N sub-domains on GPU 0 (the emulator analogue
 // of --device ipumodel: exercises the multi-GPU halo path on one device).
 // --device cpu runs the same fused step on the host's cores (lbm_cpu.hpp:
 // OpenMP rows, bitwise equal to the GPU engine's default numerics); the
-// GPU-only options (-n, --tolerance, --kernel, --spl, --graph-steps, --device-fields, --mean-every, --scalar, --buoyancy, --transport, --scalar-walls) do not
+// GPU-only options (-n, --tolerance, --kernel, --spl, --graph-steps, --device-fields, --mean-every, --scalar, --buoyancy, --transport, --scalar-walls, --forcing) do not
 // apply there and are refused with a message.
 #include <algorithm>
 #include <cstdio>
@@ -98,6 +106,7 @@
 #include "lbm_binned_hip.h"
 #include "lbm_cpu.hpp"
 #include "lbm_forces_hip.h"
+#include "lbm_forcing_hip.h"
 #include "lbm_gradients_hip.h"
 #include "lbm_host.hpp"
 #include "lbm_scalar_hip.h"
@@ -156,6 +165,11 @@ void usage(const char *exe) {
               << "                       for --forces), and also write wall_flux.dat: body kind value q links\n"
               << "      --transport arg  BWxBH: with --scalar, also write transport_state.dat: per bin of BW x BH cells the\n"
               << "                       fluid cells and the sums of phi, phi^2, ux phi, uy phi and the face fluxes FX, FY\n"
+              << "      --forcing arg    file of `zone x0 y0 w h lam utx uty fx fy` lines: forcing zones (a drag lam towards\n"
+              << "                       the velocity (utx, uty) and an acceleration (fx, fy) on a box of cells) applied\n"
+              << "                       through the first run, and also write forcing.dat: zone ix iy, the momentum added\n"
+              << "      --forcing-stride arg  flow steps between two applications of the zones, each the impulse of as\n"
+              << "                       many steps (default: 1)\n"
               << "      --out-dir arg    directory for av_vels.dat / final_state.dat (default: .)\n"
               << "      --graph-steps arg  replay the step loop as hipGraphs of 2*arg launches (0 = library default, <0 = off)\n"
               << "      --dump-partitioning arg  write the sub-domain decomposition as JSON\n"
@@ -274,6 +288,8 @@ int main(int argc, char *argv[]) {
     double buoyancyX = 0.0, buoyancyY = 0.0;
     float scalarRef = 0.f;
     int transW = 0, transH = 0;
+    std::string forcingFile;
+    int forcingStride = 1;
     std::vector<std::string> gpuOnly;  // GPU-only options given on the command line
     int spl = 0;
     int numGpus = 1, runs = 5, graphSteps = 0, meanEvery = 0, binW = 0, binH = 0;
@@ -382,6 +398,14 @@ int main(int argc, char *argv[]) {
             if (!next(v)) { usage(argv[0]); return EXIT_FAILURE; }
             scalarRef = std::strtof(v.c_str(), nullptr);
             scalarRefGiven = true;
+            gpuOnly.push_back(a);
+        } else if (a == "--forcing") {
+            if (!next(forcingFile)) { usage(argv[0]); return EXIT_FAILURE; }
+            gpuOnly.push_back(a);
+        } else if (a == "--forcing-stride") {
+            if (!next(v)) { usage(argv[0]); return EXIT_FAILURE; }
+            forcingStride = std::atoi(v.c_str());
+            if (forcingStride < 1) { usage(argv[0]); return EXIT_FAILURE; }
             gpuOnly.push_back(a);
         } else if (a == "--out-dir") {
             if (!next(outDir)) { usage(argv[0]); return EXIT_FAILURE; }
@@ -515,6 +539,45 @@ int main(int argc, char *argv[]) {
             }
         }
     }
+    // --forcing: uniform zones, index and box checked here, the coefficients by the library
+    struct ForcingZone {
+        int zone, x0, y0, w, h;
+        float k[5];
+    };
+    std::vector<ForcingZone> forcingZones;
+    if (!forcingFile.empty()) {
+        if (meanEvery > 0 || tracers.has_value() || !scalarFile.empty()) {
+            std::cerr << "--forcing, --scalar, --tracers and --mean-every each take the run in their own chunks: give "
+                         "one of them" << std::endl;
+            return EXIT_FAILURE;
+        }
+        std::ifstream f(forcingFile);
+        if (!f) {
+            std::cerr << "--forcing: could not read the zones from " << forcingFile << std::endl;
+            return EXIT_FAILURE;
+        }
+        std::string line;
+        while (std::getline(f, line)) {
+            const size_t first = line.find_first_not_of(" \t\r");
+            if (first == std::string::npos || line[first] == '#') continue;
+            ForcingZone z{};
+            char tail = 0;
+            if (sscanf(line.c_str(), "%d %d %d %d %d %f %f %f %f %f %c", &z.zone, &z.x0, &z.y0, &z.w, &z.h, &z.k[0],
+                       &z.k[1], &z.k[2], &z.k[3], &z.k[4], &tail) != 10 ||
+                z.zone < 0 || z.zone >= LBM_FORCING_MAX_ZONES) {
+                std::cerr << "Malformed --forcing line (zone x0 y0 w h lam utx uty fx fy; zone in 0.."
+                          << LBM_FORCING_MAX_ZONES - 1 << "): " << line << std::endl;
+                return EXIT_FAILURE;
+            }
+            if (z.w < 1 || z.h < 1 || z.x0 < 0 || z.y0 < 0 || (size_t)z.x0 + z.w > params->nx ||
+                (size_t)z.y0 + z.h > params->ny) {
+                std::cerr << "--forcing: the box of zone " << z.zone << " is empty or leaves the domain: " << line
+                          << std::endl;
+                return EXIT_FAILURE;
+            }
+            forcingZones.push_back(z);
+        }
+    }
     if (!dumpFile.empty()) {
         // partitioning.json in the layout of grids::serializeToJson
         // (StructuredGridUtils.hpp:135-158), one entry per GPU sub-domain;
@@ -607,6 +670,8 @@ int main(int argc, char *argv[]) {
     lbmhost::timedStep("Running copy to device step", [&]() {
         lbmhost::check(lbm_load_cells(h, cells.data()), h, "lbm_load_cells");
     });
+    double forcingImpulse[LBM_FORCING_MAX_ZONES][2] = {};  // --forcing: forcing.dat's columns
+    uint32_t forcingMask = 0;
     if (meanEvery > 0) {
         total_compute_time += lbmhost::timedStep("Running LBM", [&]() {
             lbmhost::check(lbm_avg_begin(h, LBM_AVG_MEAN | LBM_AVG_SECOND), h, "lbm_avg_begin");
@@ -651,12 +716,33 @@ int main(int argc, char *argv[]) {
                 done += n;
             }
         });
+    } else if (!forcingFile.empty()) {
+        total_compute_time += lbmhost::timedStep("Running LBM", [&]() {
+            for (const auto &z : forcingZones)
+                lbmhost::check(lbm_forcing_set_zone(h, z.zone, z.x0, z.y0, z.w, z.h, nullptr, z.k), h,
+                               "lbm_forcing_set_zone");
+            for (int done = 0; done < (int)params->maxIters;) {
+                const int n = std::min(forcingStride, (int)params->maxIters - done);
+                double impulse[LBM_FORCING_MAX_ZONES][2];
+                lbmhost::check(lbm_forcing_apply(h, (float)n, &impulse[0][0]), h, "lbm_forcing_apply");
+                for (int z = 0; z < LBM_FORCING_MAX_ZONES; ++z) {
+                    forcingImpulse[z][0] += impulse[z][0];
+                    forcingImpulse[z][1] += impulse[z][1];
+                }
+                lbmhost::check(lbm_run_steps(h, n, done == 0), h, "lbm_run_steps");
+                lbmhost::check(lbm_store(h, nullptr, av_vels.data() + done, n), h, "lbm_store");
+                done += n;
+            }
+            lbmhost::check(lbm_forcing_zones(h, nullptr, &forcingMask), h, "lbm_forcing_zones");
+            lbmhost::check(lbm_forcing_clear(h), h, "lbm_forcing_clear");  // the timed re-runs are free runs
+        });
     } else {
         total_compute_time += lbmhost::timedStep("Running LBM", [&]() { lbmhost::check(lbm_run(h), h, "lbm_run"); });
     }
     std::vector<float> means[LBM_AVG_FIELDS];         // --mean-every: mean_state.dat's columns, planar
-    // --mean-every, --tracers and --scalar gathered av_vels per chunk: the last run's would overwrite them
-    float *const avOut = (meanEvery > 0 || tracers.has_value() || !scalarFile.empty()) ? nullptr : av_vels.data();
+    // --mean-every, --tracers, --scalar and --forcing gathered av_vels per chunk: the last run's would overwrite them
+    float *const avOut =
+        (meanEvery > 0 || tracers.has_value() || !scalarFile.empty() || !forcingFile.empty()) ? nullptr : av_vels.data();
     std::vector<float> f_ux, f_uy, f_u, f_pressure;  // --device-fields: final_state.dat's columns, planar
     lbmhost::BodyForces bodyForces;                   // --forces: forces.dat
     std::vector<float> grads[LBM_GRAD_FIELDS];        // --gradients: gradient_state.dat's columns, planar
@@ -798,6 +884,18 @@ int main(int argc, char *argv[]) {
                 for (size_t b = 0; b < wallKind.size(); ++b)
                     fprintf(out, "%zu %d %.9g %.17g %lld\n", b, (int)wallKind[b], (double)wallValue[b], wallFlux[b],
                             (long long)wallLinks[b]);
+                fclose(out);
+            }
+        }
+        if (!forcingFile.empty()) {
+            // forcing.dat: `zone ix iy` per zone set; %.17g reads back to the same double
+            FILE *out = fopen((outDir + "/forcing.dat").c_str(), "w");
+            if (!out) {
+                std::cerr << "Could not write forcing.dat" << std::endl;
+            } else {
+                for (int z = 0; z < LBM_FORCING_MAX_ZONES; ++z)
+                    if (forcingMask >> z & 1u)
+                        fprintf(out, "%d %.17g %.17g\n", z, forcingImpulse[z][0], forcingImpulse[z][1]);
                 fclose(out);
             }
         }

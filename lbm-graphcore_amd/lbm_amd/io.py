@@ -926,7 +926,12 @@ KICK_PAIRS3D = ((1, 2, (0,)), (3, 4, (1,)), (9, 14, (2,)),
 def _buoyancy_increments(phi, density, s, phi_ref, w, pairs, q):
     phi = np.asarray(phi, np.float32)
     d = phi - np.float32(phi_ref)
-    j = [(np.float32(density) * np.float32(c)) * d for c in s]
+    return _pair_increments([(np.float32(density) * np.float32(c)) * d for c in s], w, pairs, q)
+
+
+def _pair_increments(j, w, pairs, q):
+    """[None, d1 .. d(q-1)] of the momentum j = [jx, jy[, jz]] (float32 arrays): the part the buoyancy and the
+    forcing zones share."""
     a = [jc * w[0] for jc in j]
     b = [jc * w[1] for jc in j]
     inc = [None] * q
@@ -987,6 +992,83 @@ def rayleigh_number(accel, dphi, height, omega, omega_s, dims: int = 2) -> float
     diffusivity (scalar_diffusivity)."""
     nu = (1.0 / float(omega) - 0.5) / 3.0
     return float(accel) * float(dphi) * float(height) ** 3 / (nu * scalar_diffusivity(omega_s, dims))
+
+
+# ---- forcing zones (include/lbm_forcing_hip.h) ----
+#
+# One zone applied to AoS cells in fp32 numpy, one ufunc per operation.  The pair tables are the
+# buoyancy's (KICK_W, KICK_PAIRS); they, the momentum tables and forcing_momentum are read at call
+# time: a test plants an error by replacing one.
+
+# per component (speeds added, speeds subtracted), each group summed left to right: cell_momentum / cell3_momentum
+FORCING_J = (((1, 5, 8), (3, 6, 7)), ((2, 5, 6), (4, 7, 8)))
+FORCING_J3D = (((1, 5, 7, 10, 16), (2, 6, 8, 11, 15)), ((3, 5, 8, 12, 18), (4, 6, 7, 13, 17)),
+               ((9, 10, 11, 12, 13), (14, 15, 16, 17, 18)))
+
+
+def forcing_momentum(l, rho, ut, j, g):
+    """m = (l * ((rho * ut) - j)) + (rho * g): what a zone adds to one momentum component of a cell."""
+    return (l * ((rho * ut) - j)) + (rho * g)
+
+
+def _forcing_kick(cells, obst, box, coef, n, dims, w, pairs, jtable):
+    q = 9 if dims == 2 else 19
+    cells = np.array(cells, np.float32)
+    if cells.ndim != dims + 1 or cells.shape[-1] != q or np.asarray(obst).shape != cells.shape[:-1]:
+        raise ValueError("cells AoS [...][q] and obst [...] of one domain")
+    box = [int(v) for v in box]
+    if len(box) != 2 * dims or len(coef) != 1 + 2 * dims:
+        raise ValueError("box = (x0, y0[, z0], w, h[, d]) and coef = (lam, ut.., f..)")
+    origin, ext = box[:dims][::-1], box[dims:][::-1]                           # slowest axis first
+    if any(e < 1 or o < 0 or o + e > s for o, e, s in zip(origin, ext, cells.shape)):
+        raise ValueError("the box is not empty and lies inside the domain")
+    n = np.float32(n)
+    if not (np.isfinite(n) and n >= 0):
+        raise ValueError("n is finite and not negative")
+    k = [np.broadcast_to(np.asarray(c, np.float32), ext) for c in coef]
+    if not all(np.isfinite(c).all() for c in k) or (k[0] < 0).any():
+        raise ValueError("finite coefficients and lam >= 0")
+    terms = np.zeros(tuple(ext) + (dims,), np.float32)
+    if n == 0:
+        return cells, terms                       # no launch: every bit stays
+    sl = tuple(slice(o, o + e) for o, e in zip(origin, ext))
+    c = cells[sl]                                 # a view: the box is kicked in place in the copy
+    with np.errstate(all="ignore"):               # hard states: Inf and NaN under obstacles are selected away
+        l = np.minimum(n * k[0], np.float32(1))
+        g = [n * k[1 + dims + i] for i in range(dims)]
+        idle = (np.asarray(obst)[sl] != 0) | ((l == 0) & np.logical_and.reduce([gi == 0 for gi in g]))
+        rho = c[..., 0]
+        for i in range(1, q):
+            rho = rho + c[..., i]
+        m = []
+        for i, (plus, minus) in enumerate(jtable):
+            a = c[..., plus[0]]
+            for s in plus[1:]:
+                a = a + c[..., s]
+            b = c[..., minus[0]]
+            for s in minus[1:]:
+                b = b + c[..., s]
+            m.append(forcing_momentum(l, rho, k[1 + i], a - b, g[i]))
+        inc = _pair_increments(m, w, pairs, q)
+        for s in range(1, q):
+            c[..., s] = np.where(idle, c[..., s], c[..., s] + inc[s])
+        for i in range(dims):
+            terms[..., i] = np.where(idle, np.float32(0), m[i])
+    return cells, terms
+
+
+def forcing_kick(cells, obst, box, coef, n):
+    """(kicked copy of the AoS cells float32[ny][nx][9], terms float32[h][w][2]): one forcing zone applied once,
+    lbm_forcing_apply(n) on a handle whose only zone is box = (x0, y0, w, h) with coef = (lam, utx, uty, fx, fy),
+    each a number or an array [h][w].  terms holds (mx, my) of every cell of the box, zeros where it is idle
+    (obstacle, or no drag and no force); their sum is the impulse.  Idle cells keep their bits."""
+    return _forcing_kick(cells, obst, box, coef, n, 2, KICK_W, KICK_PAIRS, FORCING_J)
+
+
+def forcing_kick3d(cells, obst, box, coef, n):
+    """lbm3d_forcing_apply: cells float32[nz][ny][nx][19], box = (x0, y0, z0, w, h, d),
+    coef = (lam, utx, uty, utz, fx, fy, fz), arrays [d][h][w], terms float32[d][h][w][3]."""
+    return _forcing_kick(cells, obst, box, coef, n, 3, KICK_W3D, KICK_PAIRS3D, FORCING_J3D)
 
 
 # ---- scalar transport sums (include/lbm_transport_hip.h) ----

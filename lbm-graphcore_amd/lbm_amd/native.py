@@ -142,6 +142,13 @@ EXPORTED_WALLS = [
     "lbm3d_scalar_set_walls", "lbm3d_scalar_wall_flux", "lbm3d_scalar_body_flux", "lbm3d_scalar_store_wall_flux",
     "lbm3d_scalar_walls_ref",
 ]
+# every symbol include/lbm_forcing_hip.h declares (forcing zones: body force, drag, velocity target; both engines)
+EXPORTED_FORCING = [
+    "lbm_forcing_set_zone", "lbm_forcing_clear", "lbm_forcing_zones", "lbm_forcing_apply", "lbm_forcing_kick_ref",
+    "lbm3d_forcing_set_zone", "lbm3d_forcing_clear", "lbm3d_forcing_zones", "lbm3d_forcing_apply",
+    "lbm3d_forcing_kick_ref",
+]
+FORCING_MAX_ZONES = 8                     # LBM_FORCING_MAX_ZONES
 SCALAR_WALL_ADIABATIC, SCALAR_WALL_VALUE, SCALAR_WALL_FLUX = 0, 1, 2   # LBM_SCALAR_WALL_*
 SCALAR_WALL_KINDS = {"adiabatic": SCALAR_WALL_ADIABATIC, "value": SCALAR_WALL_VALUE, "flux": SCALAR_WALL_FLUX}
 Q3 = 19
@@ -402,6 +409,18 @@ def load_library() -> ctypes.CDLL:
         "lbm3d_scalar_body_flux": ([H, f64p, i64p, i32], ctypes.c_int),
         "lbm3d_scalar_store_wall_flux": ([H, f32p], ctypes.c_int),
         "lbm3d_scalar_walls_ref": ([i32, i32, i32, u8p, i32p, i32, i32p, f32p, f32p, f32p], ctypes.c_int),
+        # include/lbm_forcing_hip.h
+        "lbm_forcing_set_zone": ([H] + [i32] * 5 + [f32pp, f32p], ctypes.c_int),
+        "lbm_forcing_clear": ([H], ctypes.c_int),
+        "lbm_forcing_zones": ([H, i32p, ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+        "lbm_forcing_apply": ([H, ctypes.c_float, f64p], ctypes.c_int),
+        "lbm_forcing_kick_ref": ([i32, i32, u8p, f32p] + [i32] * 4 + [f32pp, f32p, ctypes.c_float, f32p], ctypes.c_int),
+        "lbm3d_forcing_set_zone": ([H] + [i32] * 7 + [f32pp, f32p], ctypes.c_int),
+        "lbm3d_forcing_clear": ([H], ctypes.c_int),
+        "lbm3d_forcing_zones": ([H, i32p, ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+        "lbm3d_forcing_apply": ([H, ctypes.c_float, f64p], ctypes.c_int),
+        "lbm3d_forcing_kick_ref": ([i32, i32, i32, u8p, f32p] + [i32] * 6 + [f32pp, f32p, ctypes.c_float, f32p],
+                                   ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -575,6 +594,62 @@ def scalar_buoyancy_ref(cells, g, obst, density, s, phi_ref=0.0):
 def scalar_buoyancy3d_ref(cells, g, obst, density, s, phi_ref=0.0):
     """lbm3d_scalar_buoyancy_ref: cells float32[nz][ny][nx][19].  lio.buoyancy_kick3d restates it."""
     return _buoyancy_ref("lbm3d_scalar_buoyancy_ref", Q3, SCALAR_Q3D, cells, g, obst, density, s, phi_ref)
+
+
+def _forcing_coefs(dims, ext, lam, target, force):
+    """(arrays kept alive, pointer table float *[1 + 2 dims], constants float[1 + 2 dims]) of a zone's
+    coefficients in header order: each of lam, target[i], force[i] a number (a constant) or an array of the
+    box's shape `ext` (slowest axis first)."""
+    target = [0.0] * dims if target is None else list(target)
+    force = [0.0] * dims if force is None else list(force)
+    if len(target) != dims or len(force) != dims:
+        raise ValueError(f"target and force have {dims} components")
+    keep, ptrs, konst = [], [], []
+    for c in [lam] + target + force:
+        if np.ndim(c) == 0:
+            ptrs.append(None)
+            konst.append(float(c))
+        else:
+            a = np.ascontiguousarray(c, np.float32)
+            if a.shape != tuple(ext):
+                raise ValueError(f"a coefficient array has the box's shape {tuple(ext)}; got {a.shape}")
+            keep.append(a)
+            ptrs.append(_ptr(a))
+            konst.append(0.0)
+    n = 1 + 2 * dims
+    return keep, (ctypes.POINTER(ctypes.c_float) * n)(*ptrs), (ctypes.c_float * n)(*konst)
+
+
+def _forcing_ref(name, q, cells, obst, box, lam, target, force, n):
+    cells = np.array(cells, np.float32, order="C")
+    dims = cells.ndim - 1
+    obst = np.ascontiguousarray(obst, np.uint8)
+    box = [int(v) for v in box]
+    if cells.shape[-1] != q or obst.shape != cells.shape[:-1] or len(box) != 2 * dims:
+        raise ValueError("cells [..][q] and obst [..] of one domain, box = (x0, y0[, z0], w, h[, d])")
+    ext = box[dims:][::-1]
+    if min(ext) < 1:
+        raise ValueError("the box is not empty")
+    keep, table, konst = _forcing_coefs(dims, ext, lam, target, force)
+    terms = np.zeros(tuple(ext) + (dims,), np.float32)
+    rc = getattr(load_library(), name)(*cells.shape[:-1][::-1], _ptr(obst), _ptr(cells), *box, table, konst,
+                                       float(n), _ptr(terms))
+    if rc != LBM_OK:
+        raise LbmError(rc, name + ": invalid argument")
+    return cells, terms
+
+
+def forcing_kick_ref(cells, obst, box, lam=0.0, target=None, force=None, n=1.0):
+    """(kicked copy of the AoS cells float32[ny][nx][9], terms float32[h][w][2]): lbm_forcing_kick_ref -- the
+    C++ per-cell function of the kernel, compiled for the host (no GPU) -- of one zone box = (x0, y0, w, h).
+    lio.forcing_kick restates it."""
+    return _forcing_ref("lbm_forcing_kick_ref", 9, cells, obst, box, lam, target, force, n)
+
+
+def forcing_kick3d_ref(cells, obst, box, lam=0.0, target=None, force=None, n=1.0):
+    """lbm3d_forcing_kick_ref: cells float32[nz][ny][nx][19], box = (x0, y0, z0, w, h, d).  lio.forcing_kick3d
+    restates it."""
+    return _forcing_ref("lbm3d_forcing_kick_ref", Q3, cells, obst, box, lam, target, force, n)
 
 
 def _terms_ref(name, names, qs, g, u, obst):
@@ -1354,7 +1429,80 @@ class _Scalar:
                 "q": np.stack(samples) if samples else np.zeros((0, self._scalar_nbodies)), "links": links}
 
 
-class Engine(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers, _Scalar):
+class _Forcing:
+    """Forcing zones (include/lbm_forcing_hip.h): a body force, a linear drag and a velocity target on boxes
+    of cells, applied as an impulse on the stored populations between runs.  Both engines."""
+
+    def forcing_zone(self, index: int, origin, shape=None, lam=0.0, target=None, force=None) -> None:
+        """Set zone `index` (0 .. 7) to the box of `shape` = (w, h[, d]) cells at `origin` = (x0, y0[, z0])
+        (shape None: from the origin to the domain's far corner; an extent 0 removes the zone).  Per cell and
+        flow step the zone closes the share `lam` of the gap between the cell's velocity and `target`
+        = (utx, uty[, utz]) and accelerates it by `force` = (fx, fy[, fz]); each of lam and the components is
+        a number or a float32 array of the box's shape, slowest axis first ([h][w] or [d][h][w])."""
+        dims = len(self._shape())
+        origin = [int(v) for v in origin]
+        if len(origin) != dims:
+            raise ValueError(f"origin has {dims} components")
+        if shape is None:
+            shape = [n - o for n, o in zip(self._shape()[::-1], origin)]
+        shape = [int(v) for v in shape]
+        if len(shape) != dims:
+            raise ValueError(f"shape has {dims} components")
+        keep, table, konst = _forcing_coefs(dims, shape[::-1], lam, target, force)
+        self._check(self._fn("forcing_set_zone")(self._h, int(index), *origin, *shape, table, konst))
+
+    def forcing_clear(self) -> None:
+        """Remove every zone and free its coefficients."""
+        self._check(self._fn("forcing_clear")(self._h))
+
+    def forcing_zones(self):
+        """The indices of the zones set, ascending."""
+        n, mask = ctypes.c_int32(), ctypes.c_uint32()
+        self._check(self._fn("forcing_zones")(self._h, ctypes.byref(n), ctypes.byref(mask)))
+        out = [i for i in range(FORCING_MAX_ZONES) if mask.value >> i & 1]
+        assert len(out) == n.value
+        return out
+
+    def forcing_apply(self, steps: float = 1.0, impulse: bool = False):
+        """Apply every zone once, in index order, as the impulse of `steps` flow steps: lio.forcing_kick[3d] of
+        store(), zone after zone, bit for bit.  A run afterwards continues as from load_cells of the kicked
+        cells.  impulse=True returns float64[8][dims], the momentum each zone added (rows of unset zones 0);
+        else None.  steps = 0 or no zone launches nothing."""
+        out = np.zeros((FORCING_MAX_ZONES, len(self._shape())), np.float64) if impulse else None
+        self._check(self._fn("forcing_apply")(self._h, float(steps), _ptr(out) if impulse else None))
+        return out
+
+    def run_forced(self, steps: int, stride: int = 1, accelerate_first: bool = False):
+        """Advance the flow under the zones: per chunk of n <= stride steps "forcing_apply(n), then
+        run_steps(n)" (the remainder last).  stride = 1 is the exact first-order splitting; a larger stride
+        applies the impulse of n steps at once and keeps the flow on its fused launches.  Returns the
+        float32[steps] concatenation of the chunks' average velocities (D3Q19: empty).  To drive a thermal run
+        through zones as well, compose by hand: per chunk forcing_apply(n), scalar_buoyancy(n * accel),
+        run_steps(n), scalar_advance(n); run_thermal itself knows nothing of the zones."""
+        return self._chunks(steps, stride, accelerate_first, True, lambda n, done: None,
+                            before=lambda n: self.forcing_apply(n))
+
+    def forcing_history(self, steps: int, every: int, stride: int = 1, accelerate_first: bool = False):
+        """run_forced(every, stride) chunk after chunk (the remainder last) with the impulse taken at every
+        application: a list of (step, float64[8][dims] impulse summed over the chunk).  accelerate_first
+        applies to the first chunk (D2Q9)."""
+        steps, every = int(steps), int(every)
+        if steps < 0 or every < 1:
+            raise ValueError("steps >= 0 and every >= 1")
+        out, done = [], 0
+        while done < steps:
+            n = min(every, steps - done)
+            total = np.zeros((FORCING_MAX_ZONES, len(self._shape())), np.float64)
+
+            def kick(m, total=total):
+                total += self.forcing_apply(m, impulse=True)
+            self._chunks(n, stride, accelerate_first and done == 0, False, lambda m, d: None, before=kick)
+            done += n
+            out.append((done, total))
+        return out
+
+
+class Engine(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers, _Scalar, _Forcing):
     """One lbm_handle: the HIP counterpart of the reference's poplar::Engine."""
 
     _PREFIX = "lbm_"
@@ -1576,7 +1724,7 @@ class Engine(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tra
         return "tolerance" if int(self._L.lbm_numerics(self._h)) == 1 else "bitwise"
 
 
-class Engine3D(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers, _Scalar):
+class Engine3D(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers, _Scalar, _Forcing):
     """One lbm3d_handle: the D3Q19 extension engine (include/lbm3d_hip.h)."""
 
     _PREFIX = "lbm3d_"
