@@ -695,6 +695,7 @@ void lbm3d_handle::destroy() {
     tracer_end();
     scalar_end();
     forcing_clear();
+    sgs_clear();
     grad_release();
     stress_release();
     for (auto &s : slabs) {

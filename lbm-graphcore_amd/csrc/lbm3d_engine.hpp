@@ -18,6 +18,8 @@
 //                      lbm_scalar_walls.hpp);
 //   lbm3d_forcing.hip  forcing zones: body force, drag and velocity target on boxes of cells (kernel, host
 //                      side; shared parts in lbm_forcing.hpp);
+//   lbm3d_sgs.hip      sub-grid model: a local relaxation rate by rescaling the stored non-equilibrium part
+//                      (kernel, host side; shared parts in lbm_sgs.hpp);
 //   lbm3d_abi.hip      the extern "C" functions and the RCCL posting order.
 // The diagnostics units (fields to binned) share their host paths through
 // lbm_diag_host.hpp and their cell reads and block fold through lbm_quad.hpp.
@@ -50,6 +52,9 @@ struct State;  // scalar lattice of a handle that carries a passive scalar (lbm_
 }
 namespace forcing {
 struct State;  // zones of a handle that set a forcing zone (lbm_forcing.hpp)
+}
+namespace sgs {
+struct State;  // model of a handle that set a sub-grid model (lbm_sgs.hpp)
 }
 namespace grad {
 struct Grad3Args;  // lbm_gradients.hpp
@@ -323,4 +328,10 @@ struct lbm3d_handle {
     void forcing_clear();
     void forcing_zones(int32_t *n_set, uint32_t *mask) const;
     void forcing_apply(float steps, double *impulse);
+    // lbm3d_sgs.hip (include/lbm_sgs_hip.h)
+    lbm::sgs::State *sgs = nullptr;  // built at the first model set
+    void sgs_set(int mode, float konst, const float *coef);
+    void sgs_clear();
+    void sgs_apply(float steps, double *stats);
+    void sgs_store_nut(float *nut);
 };

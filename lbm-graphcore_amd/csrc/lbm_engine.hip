@@ -931,6 +931,7 @@ void lbm_handle::destroy() {
     tracer_end();
     scalar_end();
     forcing_clear();
+    sgs_clear();
     grad_release();
     stress_release();
     for (auto &s : subs) {

@@ -30,6 +30,10 @@
 //                         target on boxes of cells, an impulse on the current
 //                         lattice (kernel, host side; shared parts in
 //                         lbm_forcing.hpp);
+//   lbm_sgs.hip           sub-grid model: a local relaxation rate by rescaling
+//                         the stored non-equilibrium part of the current
+//                         lattice (kernel, host side; shared parts in
+//                         lbm_sgs.hpp);
 //   lbm_exchange.hip      partition rule, torus neighbours, halo destinations,
 //                         the posted exchange (RCCL or device copies);
 //   lbm_split.hip         work decomposition: boundary / interior split,
@@ -134,6 +138,11 @@ struct State;  // scalar lattice of a handle that carries a passive scalar (lbm_
 }
 namespace forcing {
 struct State;  // zones of a handle that set a forcing zone (lbm_forcing.hpp)
+}
+namespace sgs {
+struct State;  // model of a handle that set a sub-grid model (lbm_sgs.hpp)
+struct Model;
+struct Sgs2;   // lbm_sgs.hip
 }
 namespace stress {
 struct State;       // near-wall class maps of a handle that asked for strain statistics (lbm_stress.hip)
@@ -509,5 +518,12 @@ struct lbm_handle {
     void forcing_clear();
     void forcing_zones(int32_t *n_set, uint32_t *mask) const;
     void forcing_apply(float steps, double *impulse);
+    // sub-grid model (lbm_sgs.hip; include/lbm_sgs_hip.h)
+    lbm::sgs::State *sgs = nullptr;  // built at the first model set
+    lbm::sgs::Sgs2 sgs_args(const Sub &s, const lbm::sgs::Model &m) const;
+    void sgs_set(int mode, float konst, const float *coef);
+    void sgs_clear();
+    void sgs_apply(float steps, double *stats);
+    void sgs_store_nut(float *nut);
     void destroy();
 };

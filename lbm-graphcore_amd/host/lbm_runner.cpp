@@ -6,6 +6,7 @@
 //              [--tolerance] [--device-fields] [--forces] [--mean-every N] [--gradients] [--stress] [--binned BWxBH]
 //              [--tracers FILE [--trace-every N] [--trace-scheme euler|heun]]
 //              [--forcing FILE [--forcing-stride N]]
+//              [--sgs smagorinsky:CS|omega:W [--sgs-stride N]]
 //              [--scalar FILE [--scalar-omega W] [--scalar-stride N] [--buoyancy GX,GY] [--scalar-ref R]
 //                             [--transport BWxBH] [--scalar-walls FILE2]]
 //              [--json FILE]
@@ -84,11 +85,19 @@
 // of n steps (lbm_forcing_hip.h: lbm_forcing_apply).  It writes forcing.dat
 // after the run: `zone ix iy` per zone, the momentum the zone added summed
 // over the run, in %.17g.  The timed re-runs are free runs.  GPU only.
+// --sgs smagorinsky:CS | omega:W sets a sub-grid model (a Smagorinsky eddy
+// viscosity with the constant CS, or the relaxation rate W everywhere) and runs
+// the first run through the LES loop: behind every chunk of
+// n <= --sgs-stride (default 1) steps the model is applied for n steps
+// (lbm_sgs_hip.h: lbm_sgs_apply).  It writes sgs.dat after the run: per
+// application `step cells mean max`, the steps done, the cells the model
+// changed and the mean and the largest viscosity it added to them, in %.17g.
+// The timed re-runs are free runs.  GPU only.
 // --device loopback places all N sub-domains on GPU 0 (the emulator analogue
 // of --device ipumodel: exercises the multi-GPU halo path on one device).
 // --device cpu runs the same fused step on the host's cores (lbm_cpu.hpp:
 // OpenMP rows, bitwise equal to the GPU engine's default numerics); the
-// GPU-only options (-n, --tolerance, --kernel, --spl, --graph-steps, --device-fields, --mean-every, --scalar, --buoyancy, --transport, --scalar-walls, --forcing) do not
+// GPU-only options (-n, --tolerance, --kernel, --spl, --graph-steps, --device-fields, --mean-every, --scalar, --buoyancy, --transport, --scalar-walls, --forcing, --sgs) do not
 // apply there and are refused with a message.
 #include <algorithm>
 #include <cstdio>
@@ -111,6 +120,7 @@
 #include "lbm_host.hpp"
 #include "lbm_scalar_hip.h"
 #include "lbm_scalar_walls_hip.h"
+#include "lbm_sgs_hip.h"
 #include "lbm_transport_hip.h"
 #include "lbm_stress_hip.h"
 #include "lbm_tracers_hip.h"
@@ -170,6 +180,11 @@ void usage(const char *exe) {
               << "                       through the first run, and also write forcing.dat: zone ix iy, the momentum added\n"
               << "      --forcing-stride arg  flow steps between two applications of the zones, each the impulse of as\n"
               << "                       many steps (default: 1)\n"
+              << "      --sgs arg        smagorinsky:CS or omega:W: a sub-grid model (Smagorinsky constant CS, or the relaxation\n"
+              << "                       rate W on every cell) applied through the first run, and also write sgs.dat: step\n"
+              << "                       cells mean max, the cells changed and the viscosity added at every application\n"
+              << "      --sgs-stride arg flow steps between two applications of the model, each standing for as many steps\n"
+              << "                       (default: 1)\n"
               << "      --out-dir arg    directory for av_vels.dat / final_state.dat (default: .)\n"
               << "      --graph-steps arg  replay the step loop as hipGraphs of 2*arg launches (0 = library default, <0 = off)\n"
               << "      --dump-partitioning arg  write the sub-domain decomposition as JSON\n"
@@ -290,6 +305,9 @@ int main(int argc, char *argv[]) {
     int transW = 0, transH = 0;
     std::string forcingFile;
     int forcingStride = 1;
+    std::string sgsSpec;
+    int sgsMode = LBM_SGS_OFF, sgsStride = 1;
+    float sgsCoef = 0.f;
     std::vector<std::string> gpuOnly;  // GPU-only options given on the command line
     int spl = 0;
     int numGpus = 1, runs = 5, graphSteps = 0, meanEvery = 0, binW = 0, binH = 0;
@@ -406,6 +424,23 @@ int main(int argc, char *argv[]) {
             if (!next(v)) { usage(argv[0]); return EXIT_FAILURE; }
             forcingStride = std::atoi(v.c_str());
             if (forcingStride < 1) { usage(argv[0]); return EXIT_FAILURE; }
+            gpuOnly.push_back(a);
+        } else if (a == "--sgs") {
+            if (!next(sgsSpec)) { usage(argv[0]); return EXIT_FAILURE; }
+            const size_t colon = sgsSpec.find(':');
+            const std::string kind = sgsSpec.substr(0, colon);
+            char *end = nullptr;
+            if (colon != std::string::npos) sgsCoef = std::strtof(sgsSpec.c_str() + colon + 1, &end);
+            sgsMode = kind == "smagorinsky" ? LBM_SGS_SMAGORINSKY : kind == "omega" ? LBM_SGS_OMEGA : LBM_SGS_OFF;
+            if (sgsMode == LBM_SGS_OFF || !end || end == sgsSpec.c_str() + colon + 1 || *end) {
+                std::cerr << "Malformed --sgs (smagorinsky:CS or omega:W): " << sgsSpec << std::endl;
+                return EXIT_FAILURE;
+            }
+            gpuOnly.push_back(a);
+        } else if (a == "--sgs-stride") {
+            if (!next(v)) { usage(argv[0]); return EXIT_FAILURE; }
+            sgsStride = std::atoi(v.c_str());
+            if (sgsStride < 1) { usage(argv[0]); return EXIT_FAILURE; }
             gpuOnly.push_back(a);
         } else if (a == "--out-dir") {
             if (!next(outDir)) { usage(argv[0]); return EXIT_FAILURE; }
@@ -578,6 +613,12 @@ int main(int argc, char *argv[]) {
             forcingZones.push_back(z);
         }
     }
+    if (sgsMode != LBM_SGS_OFF &&
+        (meanEvery > 0 || tracers.has_value() || !scalarFile.empty() || !forcingFile.empty())) {
+        std::cerr << "--sgs, --forcing, --scalar, --tracers and --mean-every each take the run in their own chunks: give "
+                     "one of them" << std::endl;
+        return EXIT_FAILURE;
+    }
     if (!dumpFile.empty()) {
         // partitioning.json in the layout of grids::serializeToJson
         // (StructuredGridUtils.hpp:135-158), one entry per GPU sub-domain;
@@ -672,6 +713,11 @@ int main(int argc, char *argv[]) {
     });
     double forcingImpulse[LBM_FORCING_MAX_ZONES][2] = {};  // --forcing: forcing.dat's columns
     uint32_t forcingMask = 0;
+    struct SgsRow {
+        int step;
+        double stats[3];
+    };
+    std::vector<SgsRow> sgsRows;  // --sgs: sgs.dat's lines
     if (meanEvery > 0) {
         total_compute_time += lbmhost::timedStep("Running LBM", [&]() {
             lbmhost::check(lbm_avg_begin(h, LBM_AVG_MEAN | LBM_AVG_SECOND), h, "lbm_avg_begin");
@@ -736,13 +782,29 @@ int main(int argc, char *argv[]) {
             lbmhost::check(lbm_forcing_zones(h, nullptr, &forcingMask), h, "lbm_forcing_zones");
             lbmhost::check(lbm_forcing_clear(h), h, "lbm_forcing_clear");  // the timed re-runs are free runs
         });
+    } else if (sgsMode != LBM_SGS_OFF) {
+        total_compute_time += lbmhost::timedStep("Running LBM", [&]() {
+            lbmhost::check(lbm_sgs_set(h, sgsMode, sgsCoef, nullptr), h, "lbm_sgs_set");
+            for (int done = 0; done < (int)params->maxIters;) {
+                const int n = std::min(sgsStride, (int)params->maxIters - done);
+                lbmhost::check(lbm_run_steps(h, n, done == 0), h, "lbm_run_steps");
+                lbmhost::check(lbm_store(h, nullptr, av_vels.data() + done, n), h, "lbm_store");
+                done += n;
+                SgsRow row{done, {0.0, 0.0, 0.0}};
+                lbmhost::check(lbm_sgs_apply(h, (float)n, row.stats), h, "lbm_sgs_apply");
+                sgsRows.push_back(row);
+            }
+            lbmhost::check(lbm_sgs_set(h, LBM_SGS_OFF, 0.f, nullptr), h, "lbm_sgs_set");  // the timed re-runs are free runs
+        });
     } else {
         total_compute_time += lbmhost::timedStep("Running LBM", [&]() { lbmhost::check(lbm_run(h), h, "lbm_run"); });
     }
     std::vector<float> means[LBM_AVG_FIELDS];         // --mean-every: mean_state.dat's columns, planar
-    // --mean-every, --tracers, --scalar and --forcing gathered av_vels per chunk: the last run's would overwrite them
+    // --mean-every, --tracers, --scalar, --forcing and --sgs gathered av_vels per chunk: the last run's would overwrite them
     float *const avOut =
-        (meanEvery > 0 || tracers.has_value() || !scalarFile.empty() || !forcingFile.empty()) ? nullptr : av_vels.data();
+        (meanEvery > 0 || tracers.has_value() || !scalarFile.empty() || !forcingFile.empty() || sgsMode != LBM_SGS_OFF)
+            ? nullptr
+            : av_vels.data();
     std::vector<float> f_ux, f_uy, f_u, f_pressure;  // --device-fields: final_state.dat's columns, planar
     lbmhost::BodyForces bodyForces;                   // --forces: forces.dat
     std::vector<float> grads[LBM_GRAD_FIELDS];        // --gradients: gradient_state.dat's columns, planar
@@ -896,6 +958,18 @@ int main(int argc, char *argv[]) {
                 for (int z = 0; z < LBM_FORCING_MAX_ZONES; ++z)
                     if (forcingMask >> z & 1u)
                         fprintf(out, "%d %.17g %.17g\n", z, forcingImpulse[z][0], forcingImpulse[z][1]);
+                fclose(out);
+            }
+        }
+        if (sgsMode != LBM_SGS_OFF) {
+            // sgs.dat: `step cells mean max` per application; %.17g reads back to the same double
+            FILE *out = fopen((outDir + "/sgs.dat").c_str(), "w");
+            if (!out) {
+                std::cerr << "Could not write sgs.dat" << std::endl;
+            } else {
+                for (const auto &r : sgsRows)
+                    fprintf(out, "%d %lld %.17g %.17g\n", r.step, (long long)r.stats[0],
+                            r.stats[0] > 0 ? r.stats[1] / r.stats[0] : 0.0, r.stats[2]);
                 fclose(out);
             }
         }

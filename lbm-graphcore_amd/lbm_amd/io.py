@@ -1071,6 +1071,132 @@ def forcing_kick3d(cells, obst, box, coef, n):
     return _forcing_kick(cells, obst, box, coef, n, 3, KICK_W3D, KICK_PAIRS3D, FORCING_J3D)
 
 
+# ---- sub-grid model (include/lbm_sgs_hip.h) ----
+#
+# One application on AoS cells in fp32 numpy, one ufunc per operation.  SGS_SMAG_K, SGS_RESCALED[3D] and
+# sgs_factor are read at call time: a test plants an error by replacing one.
+
+SGS_MODES = {"smagorinsky": 1, "omega": 2}
+SGS_SMAG_K = np.float32(25.455844)                       # 18 sqrt 2
+SGS_RESCALED = tuple(range(9))                           # the speeds an application rescales: all of them
+SGS_RESCALED3D = tuple(range(19))
+# (first speed, second speed, weight: 1 axis / 2 diagonal, velocity along the first from (ux, uy[, uz]))
+SGS_PAIRS = ((1, 3, 1, lambda u: u[0]), (2, 4, 1, lambda u: u[1]),
+             (5, 7, 2, lambda u: u[0] + u[1]), (6, 8, 2, lambda u: (-u[0]) + u[1]))
+SGS_PAIRS3D = ((1, 2, 1, lambda u: u[0]), (3, 4, 1, lambda u: u[1]), (5, 6, 2, lambda u: u[0] + u[1]),
+               (7, 8, 2, lambda u: u[0] - u[1]), (9, 14, 1, lambda u: u[2]), (10, 15, 2, lambda u: u[0] + u[2]),
+               (11, 16, 2, lambda u: (-u[0]) + u[2]), (12, 17, 2, lambda u: u[1] + u[2]),
+               (13, 18, 2, lambda u: (-u[1]) + u[2]))
+# second moment of q: the diagonal sums (sequential) and the off-diagonal ((a + b) - (c + d))
+SGS_MOMENT = (((1, 3, 5, 6, 7, 8), (2, 4, 5, 6, 7, 8)), ((5, 7, 6, 8),))
+SGS_MOMENT3D = (((1, 2, 5, 6, 7, 8, 10, 11, 15, 16), (3, 4, 5, 6, 7, 8, 12, 13, 17, 18), tuple(range(9, 19))),
+                ((5, 6, 7, 8), (10, 15, 11, 16), (12, 17, 13, 18)))
+
+
+def sgs_factor(omega0, omega_eff, omo):
+    """d = (w0 - w_eff) / (1 - w0): the share of its stored non-equilibrium part a cell gains."""
+    return (omega0 - omega_eff) / omo
+
+
+def sgs_mode(mode) -> int:
+    m = SGS_MODES.get(mode, mode) if isinstance(mode, str) else mode
+    if m not in (1, 2):
+        raise ValueError(f"mode is one of {sorted(SGS_MODES)} (or 1, 2)")
+    return int(m)
+
+
+def _sgs_filter(cells, obst, omega, mode, coef, n, dims, with_idle=False):
+    q9, pairs, moment, rescaled = ((9, SGS_PAIRS, SGS_MOMENT, SGS_RESCALED) if dims == 2
+                                   else (19, SGS_PAIRS3D, SGS_MOMENT3D, SGS_RESCALED3D))
+    cells = np.array(cells, np.float32)
+    shape = cells.shape[:-1]
+    if cells.ndim != dims + 1 or cells.shape[-1] != q9 or np.asarray(obst).shape != shape:
+        raise ValueError("cells AoS [...][q] and obst [...] of one domain")
+    mode = sgs_mode(mode)
+    f32 = np.float32
+    w0, n = f32(omega), f32(n)
+    if not (np.isfinite(w0) and 0 < w0 < 2) or f32(1) - w0 == 0:
+        raise ValueError("omega lies in (0, 2) and is not 1")
+    if not (np.isfinite(n) and n >= 0):
+        raise ValueError("n is finite and not negative")
+    if np.ndim(coef) != 0 and np.shape(coef) != shape:
+        raise ValueError(f"a coefficient array has the domain's shape {shape}")
+    k = np.broadcast_to(np.asarray(coef, np.float32), shape)
+    if not np.isfinite(k).all() or (k < 0).any() or (mode == 2 and not ((k > 0) & (k < 2)).all()):
+        raise ValueError("finite coefficients: Cs >= 0, or a rate in (0, 2)")
+    nut = np.zeros(shape, np.float32)
+    if n == 0:                                     # no launch: every bit stays
+        return (cells, nut, np.ones(shape, bool)) if with_idle else (cells, nut)
+    omo, tau0 = f32(1) - w0, f32(1) / w0
+    nu0 = (tau0 - f32(0.5)) / f32(3)
+    t = [cells[..., i] for i in range(q9)]
+    with np.errstate(all="ignore"):                # hard states: Inf and NaN under obstacles are selected away
+        if dims == 2:
+            rho = _seq([f32(0)] + t, *range(q9 + 1))
+            u = [(_seq(t, *a) - _seq(t, *b)) / rho for a, b in FORCING_J]
+            usq = (u[0] * u[0]) + (u[1] * u[1])
+            lw = ((f32(4) / f32(9)) * rho, rho / f32(9), rho / f32(36))
+        else:
+            rho = _seq(t, *range(q9))
+            u = [(_seq(t, *a) - _seq(t, *b)) / rho for a, b in FORCING_J3D]
+            usq = ((u[0] * u[0]) + (u[1] * u[1])) + (u[2] * u[2])
+            lw = (rho / f32(3), rho / f32(18), rho / f32(36))
+        csq = f32(1) - (usq * f32(1.5))
+        two3 = f32(2) / f32(3)
+        q = [None] * q9
+        q[0] = t[0] - (lw[0] * csq)
+        for a, b, wi, vel in pairs:
+            v = vel(u)
+            q[a] = t[a] - (lw[wi] * (((f32(4.5) * v) * (two3 + v)) + csq))
+            q[b] = t[b] - (lw[wi] * (((f32(-4.5) * v) * (two3 - v)) + csq))
+        diag = [_seq(q, *ks) for ks in moment[0]]
+        off = [(q[a] + q[b]) - (q[c] + q[d]) for a, b, c, d in moment[1]]
+        p2 = _seq([x * x for x in diag], *range(len(diag))) + (_seq([x * x for x in off], *range(len(off))) * f32(2))
+        pim = np.sqrt(p2, dtype=np.float32) / np.abs(omo)
+        if mode == 1:
+            a = (SGS_SMAG_K * n) * (k * k)
+            tau = f32(0.5) * (tau0 + np.sqrt((tau0 * tau0) + ((a * pim) / rho), dtype=np.float32))
+            off_cell = k == 0
+        else:
+            nu1 = ((f32(1) / k) - f32(0.5)) / f32(3)
+            tau = (f32(3) * (nu0 + (n * (nu1 - nu0)))) + f32(0.5)
+            tau = np.broadcast_to(tau, shape)
+            off_cell = k == w0
+            we = f32(1) / tau
+            if not ((we > 0) & (we < 2)).all():
+                raise ValueError("the rate an application ends with lies in (0, 2)")
+        we = f32(1) / tau
+        d = sgs_factor(w0, we, omo)
+        idle = (np.asarray(obst) != 0) | off_cell | (d == 0)
+        nut = np.where(idle, f32(0), (tau - tau0) / f32(3)).astype(np.float32)
+        for i in rescaled:
+            cells[..., i] = np.where(idle, t[i], t[i] + (d * q[i]))
+    return (cells, nut, idle) if with_idle else (cells, nut)
+
+
+def sgs_filter(cells, obst, omega, mode, coef, n=1.0, with_idle=False):
+    """(filtered copy of the AoS cells float32[ny][nx][9], nut float32[ny][nx]): one lbm_sgs_apply(n) on a
+    lattice that was collided with `omega`, mode "smagorinsky" (coef = Cs) or "omega" (coef = the rate wanted),
+    coef a number or an array [ny][nx].  nut is nu_add of every cell, 0 where it is idle (obstacle, Cs = 0 or
+    rate = omega, or a factor d of exactly 0); idle cells keep their bits.  with_idle=True appends the bool
+    map of the idle cells."""
+    return _sgs_filter(cells, obst, omega, mode, coef, n, 2, with_idle)
+
+
+def sgs_filter3d(cells, obst, omega, mode, coef, n=1.0, with_idle=False):
+    """lbm3d_sgs_apply: cells float32[nz][ny][nx][19], coef a number or an array [nz][ny][nx]."""
+    return _sgs_filter(cells, obst, omega, mode, coef, n, 3, with_idle)
+
+
+def sgs_stats(nut, idle):
+    """(cells, sum, max) as lbm_sgs_apply's stats give them, from the nut and the idle map of an application
+    (with_idle=True): the cells that were not idle, the float64 sum of their nu_add and the larger of 0 and
+    their largest nu_add."""
+    live = ~np.asarray(idle, bool)
+    v = np.asarray(nut, np.float32)[live]
+    return int(live.sum()), float(np.sum(v.astype(np.float64))), float(np.fmax.reduce(v, initial=np.float32(0)))
+
+
 # ---- scalar transport sums (include/lbm_transport_hip.h) ----
 #
 # The face fluxes in fp32 numpy (one subtraction), the other terms in float64 as

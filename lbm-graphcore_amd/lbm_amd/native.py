@@ -149,6 +149,13 @@ EXPORTED_FORCING = [
     "lbm3d_forcing_kick_ref",
 ]
 FORCING_MAX_ZONES = 8                     # LBM_FORCING_MAX_ZONES
+# every symbol include/lbm_sgs_hip.h declares (sub-grid model: Smagorinsky, prescribed local rate; both engines)
+EXPORTED_SGS = [
+    "lbm_sgs_set", "lbm_sgs_apply", "lbm_sgs_store_nut", "lbm_sgs_filter_ref",
+    "lbm3d_sgs_set", "lbm3d_sgs_apply", "lbm3d_sgs_store_nut", "lbm3d_sgs_filter_ref",
+]
+SGS_OFF, SGS_SMAGORINSKY, SGS_OMEGA = 0, 1, 2                            # LBM_SGS_*
+SGS_MODES = {"off": SGS_OFF, "smagorinsky": SGS_SMAGORINSKY, "omega": SGS_OMEGA}
 SCALAR_WALL_ADIABATIC, SCALAR_WALL_VALUE, SCALAR_WALL_FLUX = 0, 1, 2   # LBM_SCALAR_WALL_*
 SCALAR_WALL_KINDS = {"adiabatic": SCALAR_WALL_ADIABATIC, "value": SCALAR_WALL_VALUE, "flux": SCALAR_WALL_FLUX}
 Q3 = 19
@@ -421,6 +428,17 @@ def load_library() -> ctypes.CDLL:
         "lbm3d_forcing_apply": ([H, ctypes.c_float, f64p], ctypes.c_int),
         "lbm3d_forcing_kick_ref": ([i32, i32, i32, u8p, f32p] + [i32] * 6 + [f32pp, f32p, ctypes.c_float, f32p],
                                    ctypes.c_int),
+        # include/lbm_sgs_hip.h
+        "lbm_sgs_set": ([H, i32, ctypes.c_float, f32p], ctypes.c_int),
+        "lbm_sgs_apply": ([H, ctypes.c_float, f64p], ctypes.c_int),
+        "lbm_sgs_store_nut": ([H, f32p], ctypes.c_int),
+        "lbm_sgs_filter_ref": ([i32, i32, u8p, f32p, ctypes.c_float, i32, ctypes.c_float, f32p, ctypes.c_float, f32p],
+                               ctypes.c_int),
+        "lbm3d_sgs_set": ([H, i32, ctypes.c_float, f32p], ctypes.c_int),
+        "lbm3d_sgs_apply": ([H, ctypes.c_float, f64p], ctypes.c_int),
+        "lbm3d_sgs_store_nut": ([H, f32p], ctypes.c_int),
+        "lbm3d_sgs_filter_ref": ([i32, i32, i32, u8p, f32p, ctypes.c_float, i32, ctypes.c_float, f32p, ctypes.c_float,
+                                  f32p], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -650,6 +668,49 @@ def forcing_kick3d_ref(cells, obst, box, lam=0.0, target=None, force=None, n=1.0
     """lbm3d_forcing_kick_ref: cells float32[nz][ny][nx][19], box = (x0, y0, z0, w, h, d).  lio.forcing_kick3d
     restates it."""
     return _forcing_ref("lbm3d_forcing_kick_ref", Q3, cells, obst, box, lam, target, force, n)
+
+
+def _sgs_mode(mode, off=False) -> int:
+    m = SGS_MODES.get(mode, mode) if isinstance(mode, str) else mode
+    if m not in ((SGS_OFF, SGS_SMAGORINSKY, SGS_OMEGA) if off else (SGS_SMAGORINSKY, SGS_OMEGA)):
+        raise ValueError(f"the sub-grid mode is one of {sorted(SGS_MODES)}; got {mode!r}")
+    return int(m)
+
+
+def _sgs_coef(coef, shape):
+    """(array kept alive or None, its pointer or NULL, the constant) of a coefficient: a number, or an array
+    of the domain's shape."""
+    if np.ndim(coef) == 0:
+        return None, None, float(coef)
+    a = np.ascontiguousarray(coef, np.float32)
+    if a.shape != tuple(shape):
+        raise ValueError(f"a coefficient array has the domain's shape {tuple(shape)}; got {a.shape}")
+    return a, _ptr(a), 0.0
+
+
+def _sgs_ref(name, q, cells, obst, omega, mode, coef, n):
+    cells = np.array(cells, np.float32, order="C")
+    obst = np.ascontiguousarray(obst, np.uint8)
+    if cells.shape[-1] != q or obst.shape != cells.shape[:-1]:
+        raise ValueError("cells [..][q] and obst [..] of one domain")
+    keep, ptr, konst = _sgs_coef(coef, obst.shape)
+    nut = np.zeros(obst.shape, np.float32)
+    rc = getattr(load_library(), name)(*obst.shape[::-1], _ptr(obst), _ptr(cells), float(omega), _sgs_mode(mode),
+                                       konst, ptr, float(n), _ptr(nut))
+    if rc != LBM_OK:
+        raise LbmError(rc, name + ": invalid argument")
+    return cells, nut
+
+
+def sgs_filter_ref(cells, obst, omega, mode, coef, n=1.0):
+    """(filtered copy of the AoS cells float32[ny][nx][9], nut float32[ny][nx]): lbm_sgs_filter_ref -- the C++
+    per-cell function of the kernel, compiled for the host (no GPU).  lio.sgs_filter restates it."""
+    return _sgs_ref("lbm_sgs_filter_ref", 9, cells, obst, omega, mode, coef, n)
+
+
+def sgs_filter3d_ref(cells, obst, omega, mode, coef, n=1.0):
+    """lbm3d_sgs_filter_ref: cells float32[nz][ny][nx][19].  lio.sgs_filter3d restates it."""
+    return _sgs_ref("lbm3d_sgs_filter_ref", Q3, cells, obst, omega, mode, coef, n)
 
 
 def _terms_ref(name, names, qs, g, u, obst):
@@ -1502,7 +1563,74 @@ class _Forcing:
         return out
 
 
-class Engine(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers, _Scalar, _Forcing):
+class _Sgs:
+    """Sub-grid model (include/lbm_sgs_hip.h): a local relaxation rate -- a Smagorinsky eddy viscosity or a
+    prescribed rate that varies in space -- by rescaling the stored non-equilibrium part of every cell between
+    runs.  No step kernel changes.  Both engines."""
+
+    def sgs_model(self, kind, coef=0.0) -> None:
+        """Set the model: kind "smagorinsky" with coef = Cs (>= 0), "omega" with coef = the relaxation rate
+        wanted, in (0, 2), or "off" (frees it).  coef is a number or a float32 array of the domain's shape; a
+        cell with Cs = 0, or with the handle's own omega, is left alone (a wall-damped Cs, a viscosity sponge)."""
+        mode = _sgs_mode(kind, off=True)
+        keep, ptr, konst = (None, None, 0.0) if mode == SGS_OFF else _sgs_coef(coef, self._shape())
+        self._check(self._fn("sgs_set")(self._h, mode, konst, ptr))
+
+    def sgs_apply(self, steps: float = 1.0, stats: bool = False):
+        """One application standing for `steps` flow steps: lio.sgs_filter[3d] of store(), bit for bit.  A run
+        afterwards continues as from load_cells of the filtered cells.  stats=True returns (cells that were
+        not idle, float64 sum of their nu_add, max(0, largest nu_add)); else None.  steps = 0 or no model
+        launches nothing."""
+        out = np.zeros(3, np.float64) if stats else None
+        self._check(self._fn("sgs_apply")(self._h, float(steps), _ptr(out) if stats else None))
+        return (int(out[0]), float(out[1]), float(out[2])) if stats else None
+
+    def eddy_viscosity(self) -> np.ndarray:
+        """float32 array of the domain's shape: nu_add of every cell as sgs_apply(1) would form it from the
+        current lattice, 0 where the cell would be left alone.  The lattice is not touched.  Call it on a lattice
+        that comes from run_steps: after sgs_apply the stored non-equilibrium part is already rescaled and the
+        result is low by (1 - w_eff) / (1 - omega)."""
+        nut = np.zeros(self._shape(), np.float32)
+        self._check(self._fn("sgs_store_nut")(self._h, _ptr(nut)))
+        return nut
+
+    def run_les(self, steps: int, stride: int = 1, accelerate_first: bool = False, forced: bool = False):
+        """Advance the flow under the model: per chunk of n <= stride steps "run_steps(n), then sgs_apply(n)"
+        (the remainder last).  The filter follows the step it corrects and comes before any kick of the next
+        chunk.  stride = 1 is the exact model: every step's collision is one with the local rate.  A larger
+        stride keeps the flow on its fused launches and applies the correction of n steps at once, first-order
+        lumping as in run_forced.  forced=True puts forcing_apply(n) ahead of each chunk's run_steps(n), which
+        is run_forced under the model.  Returns the float32[steps] concatenation of the chunks' average
+        velocities (D3Q19: empty).  To combine the model with a buoyant scalar, compose by hand: per chunk
+        forcing_apply(n), scalar_buoyancy(n * accel), run_steps(n), sgs_apply(n), scalar_advance(n); run_forced
+        and run_thermal themselves know nothing of the model.  What params.accel adds (the D2Q9 inlet row, the
+        D3Q19 body force) is added after the collision and is scaled with the rest: use accel = 0 or zones."""
+        return self._chunks(steps, stride, accelerate_first, True, lambda n, done: self.sgs_apply(n),
+                            before=(lambda n: self.forcing_apply(n)) if forced else None)
+
+    def les_history(self, steps: int, every: int, stride: int = 1, accelerate_first: bool = False,
+                    forced: bool = False):
+        """run_les(every, stride, forced=forced) chunk after chunk (the remainder last) with the statistics of the last
+        application of each chunk: a list of (step, cells, mean nu_add over those cells, max nu_add)."""
+        steps, every = int(steps), int(every)
+        if steps < 0 or every < 1:
+            raise ValueError("steps >= 0 and every >= 1")
+        out, done = [], 0
+        while done < steps:
+            n = min(every, steps - done)
+            last = [(0, 0.0, 0.0)]
+
+            def after(m, d, last=last):
+                last[0] = self.sgs_apply(m, stats=True)
+            self._chunks(n, stride, accelerate_first and done == 0, False, after,
+                         before=(lambda m: self.forcing_apply(m)) if forced else None)
+            done += n
+            cells, total, peak = last[0]
+            out.append((done, cells, total / cells if cells else 0.0, peak))
+        return out
+
+
+class Engine(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers, _Scalar, _Forcing, _Sgs):
     """One lbm_handle: the HIP counterpart of the reference's poplar::Engine."""
 
     _PREFIX = "lbm_"
@@ -1724,7 +1852,7 @@ class Engine(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tra
         return "tolerance" if int(self._L.lbm_numerics(self._h)) == 1 else "bitwise"
 
 
-class Engine3D(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers, _Scalar, _Forcing):
+class Engine3D(_Handle, _WallForces, _Averages, _Gradients, _Stress, _Binned, _Tracers, _Scalar, _Forcing, _Sgs):
     """One lbm3d_handle: the D3Q19 extension engine (include/lbm3d_hip.h)."""
 
     _PREFIX = "lbm3d_"
